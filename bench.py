@@ -16,9 +16,13 @@ Workloads (`--workload`):
 Frames are independent: ranks share nothing and there is no collective on the data path (barrier + MAX/SUM reductions only).
 
 The timed region -- exactly `--steps` steps between barrier + synchronize on both sides, MAX over the ranks -- is repeated `--repeats`
-times (default 5): `value` / `ms_per_step` are the MEDIAN region, `ms_per_step_min` / `_max` and `value_min` / `_max` travel beside
-them.  `--devices 0,0` maps local ranks to devices (two ranks on one GPU: the rehearsal of the N-rank line on the hardware that
-exists); `--compose on|off` forces the waves' composition by content; `cpu_baseline` is in the line at every N (rank 0).
+times (default 1; 5 with `--full`): `value` / `ms_per_step` are the MEDIAN region, `ms_per_step_min` / `_max` and `value_min` / `_max`
+travel beside them.  `--devices 0,0` maps local ranks to devices (two ranks on one GPU: the rehearsal of the N-rank line on the hardware
+that exists); `--compose on|off` forces the waves' composition by content.
+
+A plain run sets up, warms up, checks the outputs bit-exact, times the steps and prints the line.  `--full` adds what takes runs of its
+own: per-kernel durations and the `roofline` block, the secondary figures (`--no-extras` leaves them out) and `cpu_baseline` at every N
+(rank 0; `--no-cpu-baseline` leaves it out).  `--dump-outputs DIR` writes what the last timed step computed (rank 0's share) as .npy files.
 
 One JSON line on rank 0; DESIGN.md section 5 says how `roofline` and `cpu_baseline` are derived.
 """
@@ -36,6 +40,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
+STEADY_S = 0.3             # seconds of untimed steps between the bit-exactness gate and the timed steps
 
 
 _REAL_STDOUT = None
@@ -83,8 +88,15 @@ def main():
     ap.add_argument("--pool", choices=["on", "off"], default="off",
                     help="on: merged launches take the scan and the 16-bit tier as clx_k_pool's tickets (CLX_POOL: round 6's other launch form, measured slower)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="process group backend for the barrier and the MAX / SUM reductions (nccl = RCCL)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="how often the timed region of --steps steps is repeated: `value` is the median region, min / max are carried beside it")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how often the timed region of --steps steps is repeated: `value` is the median region, min / max are carried beside it "
+                         "(default: 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: per-kernel durations and the roofline block, the secondary figures "
+                         "(unless --no-extras) and the CPU baseline (unless --no-cpu-baseline); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (a fixed, seeded sample of its frames' PCM, every frame's "
+                         "status and end bit) as DIR/<name>.npy")
     ap.add_argument("--devices", default="",
                     help="comma-separated device index per local rank (default: rank r on device r); `--gpus 2 --devices 0,0 --backend gloo` "
                          "rehearses the N-rank path -- spawn, process group, barrier, reductions, one line -- on ONE GPU")
@@ -99,6 +111,8 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no decode: only the launcher, the rank plan and the cross-rank reductions (CPU, gloo); prints a line with value null")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     # `--gpus N` by itself starts the N ranks (one process per GPU); under an external launcher (torchrun: WORLD_SIZE is set)
     # this process is one of its ranks already
@@ -217,12 +231,25 @@ def main():
     if not (bool(np.all(res["status"] == 0)) and outputs_exact(outs)):
         raise SystemExit("bench: decode is not bit-exact; refusing to report a number")
 
-    # ---- per-kernel durations: HIP events recorded by the library on the launch stream, around each of its kernels (steps one at
+    # ---- back to a steady state after the gate's host-side work: one timed region straight after it took 3-4 % longer per step than
+    #      the regions after it (MI355X, 20 steps); after a few tenths of a second of steps it takes what they do.  So the same steps
+    #      go on, a rotation at a time, until they have kept the GPU busy for STEADY_S; the timed steps' buffers are cleared below.
+    t_end = time.perf_counter() + STEADY_S
+    while time.perf_counter() < t_end:
+        for i in range(len(outs) if pipelined else 1):
+            if pipelined:
+                batch.submit(arenas[i % len(arenas)].data_ptr(), w.arena_len, outs[i].data_ptr(), stream)
+            else:
+                batch.run(d_arena.data_ptr(), w.arena_len, d_out.data_ptr(), stream)
+        batch.flush(stream)
+        torch.cuda.synchronize()
+
+    # ---- per-kernel durations (--full): HIP events recorded by the library on the launch stream, around each of its kernels (steps one at
     #      a time); they also say which kernels the library selected -- only the wave path with the latency build of the predictor keeps several steps in flight
-    kernel_ms = _kernel_ms(torch, batch, lambda: batch.run(d_arena.data_ptr(), w.arena_len, d_out.data_ptr(), stream), args.steps)
+    kernel_ms = _kernel_ms(torch, batch, lambda: batch.run(d_arena.data_ptr(), w.arena_len, d_out.data_ptr(), stream), args.steps) if args.full else {}
     kernel_ms_run = dict(kernel_ms)            # what clx_batch_run selects (config.one_step_at_a_time)
     path_tag = ""
-    if pipelined and batch.submit_lanes and "clx_k_lanes" not in kernel_ms:
+    if args.full and pipelined and batch.submit_lanes and "clx_k_lanes" not in kernel_ms:
         # the pipelined steps run the fused lane kernels while one run at a time takes the wave kernels: the roofline block is
         # about the kernels of the TIMED steps, so their durations are taken from a batch forced onto them
         bl = ctx.plan(descs, w.out_offs, verify_crc=with_crc, path=cx.PATH_LANES | cx.LANES_FUSED | (path & (cx.COMPOSE | cx.NO_COMPOSE | cx.POOL)))
@@ -235,7 +262,7 @@ def main():
     #      stream they are launched on (clx_batch_set_profiling(b, 2)) -- what `rocprofv3 --kernel-trace --stats` of
     #      tools/merge_probe.py shows (profiles/r03_config3_merged12_kernel_stats.csv)
     merged = None
-    if pipelined and batch.submit_lanes:
+    if args.full and pipelined and batch.submit_lanes:
         n_merge = max(1, batch.submit_merge)
         batch.set_profiling(2)
         acc = {}
@@ -275,6 +302,8 @@ def main():
     _, _, n_bad = shard.reduce_job(dist if use_pg else None, 0.0, 0, int((res["status"] != 0).sum()), device=red_dev)      # SUM of failed frames (must be 0)
     if n_bad:
         raise SystemExit("bench: %d frames failed to decode in the timed region" % n_bad)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, torch, w, outs[(args.steps - 1) % len(outs)], res)       # (the buffer the last timed step wrote)
     elapsed = float(np.median(regions))
     elapsed_local = float(np.median(regions_local))
     ms_per_step = 1e3 * elapsed / args.steps
@@ -285,58 +314,60 @@ def main():
         algs = [r[1] for r in per_rank]
         shard_info["imbalance"] = round(max(algs) / (sum(algs) / len(algs)) - 1.0, 5)
 
-    path_ms = float(sum(kernel_ms.values()))             # all kernels of the path, one after the other (SURVEY section 8d's t_kernel)
-    dom_name = max(kernel_ms, key=kernel_ms.get)
-    alg_bytes = w.algorithmic_bytes                      # compressed bytes read once + 4 B per decoded sample written once
-    # one step's share of the timed region is what its kernels cost the machine once they overlap the neighbouring steps';
-    # never less than max(kernel), never more than their sum when steps do not overlap
-    t_path_ms = ms_per_step if pipelined else path_ms
-    achieved = alg_bytes / (t_path_ms * 1e-3) / 1e9
-    # (which committed profile the counters come from: the fused lane kernels when the timed steps ran them -- pipelined
-    #  submissions of these workloads do --, else the kernels clx_batch_run selected)
-    timed_lanes = "clx_k_lean" in kernel_ms or "clx_k_lanes" in kernel_ms
-    traffic, traffic_src, prof = _pmc_traffic(args.workload + ("_lanes" if timed_lanes else ""), w.n)
-    roofline = {"bound": "hbm", "kernel": "+".join(kernel_ms.keys()), "achieved": round(achieved, 1), "peak": PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "path_ms": round(t_path_ms, 4), "path_ms_basis": ("ms_per_step of the pipelined steps (kernels of consecutive steps overlap)" if pipelined
-                                                                  else "sum of the path's kernel durations"),
-                "kernel_ms_sum_unpipelined": round(path_ms, 4), "kernel_ms": {k: round(v, 4) for k, v in kernel_ms.items()},
-                "kernel_ms_one_step_at_a_time": {k: round(v, 4) for k, v in kernel_ms_run.items()},
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "dominant_kernel": {"name": dom_name, "ms": round(kernel_ms[dom_name], 4),
-                                    "note": "one of the path's kernels; the path's bytes over its time alone would overstate it"},
-                "step_achieved": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-                "step_frac": round(alg_bytes / (ms_per_step * 1e-3) / 1e9 / PEAK_GBS, 4)}
-    # every rank's own fraction (its algorithmic bytes over its own step time): the line's `frac` is rank 0's share over the job's time
-    fr = [r[1] / (r[0] * 1e-3) / 1e9 / PEAK_GBS for r in per_rank if r[0] > 0]
-    if fr:
-        roofline["per_rank_frac"] = {"min": round(min(fr), 4), "max": round(max(fr), 4)}
-    if merged:
-        roofline["merged_launch"] = merged
-    if prof and prof.get("insts"):
-        # How busy the vector pipes are (round 5's measurement, profiles/r05_ubench_coissue.txt): a SIMD of gfx950
-        # takes one vector instruction per ~4.35 cycles in code like this whatever the instruction is (the 2.3-cycle rate of
-        # mov / add / shift only shows when nothing else is mixed in), and scalar, LDS and branch instructions of OTHER waves issue
-        # beside it (+0.5 .. 2 cycles per scalar instruction, ~0 per LDS instruction) -- they are NOT added on top, as rounds 3-4's
-        # flat sum (4.2 / 2.2 / 8.0 cycles) did.  So the bound is the vector instructions alone; what is left of the step is the
-        # pipes waiting: for a wave that is ready (two or three waves per SIMD), for LDS / memory round trips, for the fill and
-        # drain of the rotation.  Counts: wave-instructions per launch from the same committed --pmc profile as `traffic`.
-        ins = prof["insts"].values()
-        valu, salu, lds = (sum(k[c] for k in ins) for c in ("valu", "salu", "lds"))
-        smp = float(prof.get("samples_per_launch") or w.total_samples)
-        VALU_CYCLES, CLOCK_MHZ = 4.35, 2280.0                                # (measured: 16 slow-class VALU at 8 waves per SIMD; shader clock)
-        cyc = VALU_CYCLES * valu / 1024.0                                    # per SIMD (256 CUs x 4)
-        busy_ms = cyc / (CLOCK_MHZ * 1e3)
-        scale = w.total_samples / smp
-        roofline["issue"] = {"bound": "vector pipe (VALU issue)", "valu_per_sample": round(64.0 * valu / smp, 1), "salu_per_sample": round(64.0 * salu / smp, 1),
-                             "lds_per_sample": round(64.0 * lds / smp, 2), "valu_cycles_each": VALU_CYCLES, "clock_mhz": CLOCK_MHZ,
-                             "simd_cycles_per_launch": int(cyc * scale),
-                             "valu_busy_ms": round(busy_ms * scale, 4), "valu_busy_frac": round(busy_ms * scale / t_path_ms, 4),
-                             "waiting_frac": round(1.0 - busy_ms * scale / t_path_ms, 4),
-                             "note": "instruction counts: committed rocprofv3 --pmc profile (traffic_source); valu_busy_frac = the vector pipes' "
-                                     "busy time / time of the step; scalar and LDS instructions co-issue (profiles/r05_ubench_coissue.txt, r06_ubench_coissue.txt) and are not added; in a full machine the launches also move ~4.5 TB/s of HBM traffic against a copy ceiling of ~5 (profiles/r06_final_figures.txt): the step is bound by both"}
+    roofline = None
+    if args.full:
+        path_ms = float(sum(kernel_ms.values()))             # all kernels of the path, one after the other (SURVEY section 8d's t_kernel)
+        dom_name = max(kernel_ms, key=kernel_ms.get)
+        alg_bytes = w.algorithmic_bytes                      # compressed bytes read once + 4 B per decoded sample written once
+        # one step's share of the timed region is what its kernels cost the machine once they overlap the neighbouring steps';
+        # never less than max(kernel), never more than their sum when steps do not overlap
+        t_path_ms = ms_per_step if pipelined else path_ms
+        achieved = alg_bytes / (t_path_ms * 1e-3) / 1e9
+        # (which committed profile the counters come from: the fused lane kernels when the timed steps ran them -- pipelined
+        #  submissions of these workloads do --, else the kernels clx_batch_run selected)
+        timed_lanes = "clx_k_lean" in kernel_ms or "clx_k_lanes" in kernel_ms
+        traffic, traffic_src, prof = _pmc_traffic(args.workload + ("_lanes" if timed_lanes else ""), w.n)
+        roofline = {"bound": "hbm", "kernel": "+".join(kernel_ms.keys()), "achieved": round(achieved, 1), "peak": PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "path_ms": round(t_path_ms, 4), "path_ms_basis": ("ms_per_step of the pipelined steps (kernels of consecutive steps overlap)" if pipelined
+                                                                      else "sum of the path's kernel durations"),
+                    "kernel_ms_sum_unpipelined": round(path_ms, 4), "kernel_ms": {k: round(v, 4) for k, v in kernel_ms.items()},
+                    "kernel_ms_one_step_at_a_time": {k: round(v, 4) for k, v in kernel_ms_run.items()},
+                    "algorithmic_bytes_per_launch": alg_bytes,
+                    "dominant_kernel": {"name": dom_name, "ms": round(kernel_ms[dom_name], 4),
+                                        "note": "one of the path's kernels; the path's bytes over its time alone would overstate it"},
+                    "step_achieved": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+                    "step_frac": round(alg_bytes / (ms_per_step * 1e-3) / 1e9 / PEAK_GBS, 4)}
+        # every rank's own fraction (its algorithmic bytes over its own step time): the line's `frac` is rank 0's share over the job's time
+        fr = [r[1] / (r[0] * 1e-3) / 1e9 / PEAK_GBS for r in per_rank if r[0] > 0]
+        if fr:
+            roofline["per_rank_frac"] = {"min": round(min(fr), 4), "max": round(max(fr), 4)}
+        if merged:
+            roofline["merged_launch"] = merged
+        if prof and prof.get("insts"):
+            # How busy the vector pipes are (round 5's measurement, profiles/r05_ubench_coissue.txt): a SIMD of gfx950
+            # takes one vector instruction per ~4.35 cycles in code like this whatever the instruction is (the 2.3-cycle rate of
+            # mov / add / shift only shows when nothing else is mixed in), and scalar, LDS and branch instructions of OTHER waves issue
+            # beside it (+0.5 .. 2 cycles per scalar instruction, ~0 per LDS instruction) -- they are NOT added on top, as rounds 3-4's
+            # flat sum (4.2 / 2.2 / 8.0 cycles) did.  So the bound is the vector instructions alone; what is left of the step is the
+            # pipes waiting: for a wave that is ready (two or three waves per SIMD), for LDS / memory round trips, for the fill and
+            # drain of the rotation.  Counts: wave-instructions per launch from the same committed --pmc profile as `traffic`.
+            ins = prof["insts"].values()
+            valu, salu, lds = (sum(k[c] for k in ins) for c in ("valu", "salu", "lds"))
+            smp = float(prof.get("samples_per_launch") or w.total_samples)
+            VALU_CYCLES, CLOCK_MHZ = 4.35, 2280.0                                # (measured: 16 slow-class VALU at 8 waves per SIMD; shader clock)
+            cyc = VALU_CYCLES * valu / 1024.0                                    # per SIMD (256 CUs x 4)
+            busy_ms = cyc / (CLOCK_MHZ * 1e3)
+            scale = w.total_samples / smp
+            roofline["issue"] = {"bound": "vector pipe (VALU issue)", "valu_per_sample": round(64.0 * valu / smp, 1), "salu_per_sample": round(64.0 * salu / smp, 1),
+                                 "lds_per_sample": round(64.0 * lds / smp, 2), "valu_cycles_each": VALU_CYCLES, "clock_mhz": CLOCK_MHZ,
+                                 "simd_cycles_per_launch": int(cyc * scale),
+                                 "valu_busy_ms": round(busy_ms * scale, 4), "valu_busy_frac": round(busy_ms * scale / t_path_ms, 4),
+                                 "waiting_frac": round(1.0 - busy_ms * scale / t_path_ms, 4),
+                                 "note": "instruction counts: committed rocprofv3 --pmc profile (traffic_source); valu_busy_frac = the vector pipes' "
+                                         "busy time / time of the step; scalar and LDS instructions co-issue (profiles/r05_ubench_coissue.txt, r06_ubench_coissue.txt) and are not added; in a full machine the launches also move ~4.5 TB/s of HBM traffic against a copy ceiling of ~5 (profiles/r06_final_figures.txt): the step is bound by both"}
 
-    extras = rank == 0 and not args.no_extras
+    extras = rank == 0 and args.full and not args.no_extras
     if extras:
         # achievable-copy ceiling of this box: device-to-device copy of 1 GiB, read + write bytes
         src = torch.empty(1 << 28, dtype=torch.int32, device=dev); dst = torch.empty_like(src)
@@ -375,10 +406,12 @@ def main():
         "ms_per_step_min": round(1e3 * min(regions) / args.steps, 4), "ms_per_step_max": round(1e3 * max(regions) / args.steps, 4),
         "value_min": round(samples_all / (max(regions) / args.steps) / 1e6, 1), "value_max": round(samples_all / (min(regions) / args.steps) / 1e6, 1),
         "value_basis": "median of `repeats` timed regions of `steps` steps each (every region: barrier + synchronize on both sides, MAX over ranks)",
-        "dtype": "i32 (i64 LPC accumulate)", "data": "synthetic", "config": cfg, "roofline": roofline,
+        "dtype": "i32 (i64 LPC accumulate)", "data": "synthetic", "config": cfg,
     }
+    if roofline is not None:
+        out["roofline"] = roofline
 
-    if pipelined and not args.no_extras:
+    if args.full and pipelined and not args.no_extras:
         # ---- the same steps one at a time (clx_batch_run: nothing of step i+1 starts before step i has finished)
         el_1 = timed(batch, args.steps, False)
         el_1, samples_1, _ = shard.reduce_job(dist if use_pg else None, el_1, w.total_samples, 0, device=red_dev)
@@ -387,7 +420,7 @@ def main():
                                      "frac": round(alg_bytes / (ms_1 * 1e-3) / 1e9 / PEAK_GBS, 4),
                                      "note": "clx_batch_run (the kernels it selects: roofline.kernel_ms_one_step_at_a_time): a batch's latency; `value` is the throughput of consecutive batches with up to %d in flight" % depth}
     batch.close()                              # (its internal streams give their hardware queues back)
-    if with_crc and not args.no_extras:
+    if args.full and with_crc and not args.no_extras:
         # ---- the same step WITHOUT the CRC-16 check (what earlier rounds reported as `value`): secondary
         bc = ctx.plan(descs, w.out_offs, verify_crc=False, path=path)
         bc.run(d_arena.data_ptr(), w.arena_len, d_out.data_ptr(), stream)
@@ -419,7 +452,7 @@ def main():
             fig = _pcm16_subprocess(args, "--spaced-figure")
             if fig is not None:
                 cfg["spaced_output_blocks"] = fig
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # (at N > 1 too, on rank 0's share, behind the timed regions: north_star wants the CPU path timed in the same run at every N;
         #  the other ranks wait at the end)
         out["cpu_baseline"] = _cpu_baseline(w)
@@ -428,6 +461,25 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         _emit(json.dumps(out))
+
+
+def _dump_outputs(dirname, torch, w, d_out, res, budget_bytes=48 << 20, seed=20261015):
+    """What one timed step hands its caller, so that two builds can be compared output for output: `pcm.npy`, the decoded samples
+    (planar per frame, Claxon's Block) of a fixed, seeded sample of whole frames -- every frame when they fit `budget_bytes` -- in
+    frame order, as float32 (float64 when some frame has more than 24 bits per sample: float32 holds integers up to 2^24 exactly);
+    `pcm_frames.npy`, which frames those are; `status.npy` and `end_bit.npy`, every frame's result."""
+    os.makedirs(dirname, exist_ok=True)
+    dtype = np.float32 if int(np.max(w.bps)) <= 24 else np.float64
+    sizes = w.channels.astype(np.int64) * w.block_sizes.astype(np.int64)
+    order = np.random.default_rng(seed).permutation(w.n)
+    keep = np.sort(order[np.cumsum(sizes[order]) * np.dtype(dtype).itemsize <= budget_bytes])
+    starts, lens = np.asarray(w.out_offs, dtype=np.int64)[keep], sizes[keep]
+    idx = np.repeat(starts - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    pcm = d_out[torch.from_numpy(idx).to(d_out.device)].cpu().numpy().astype(dtype)
+    np.save(os.path.join(dirname, "pcm.npy"), pcm)
+    np.save(os.path.join(dirname, "pcm_frames.npy"), keep.astype(np.float64))
+    np.save(os.path.join(dirname, "status.npy"), res["status"].astype(np.float32))
+    np.save(os.path.join(dirname, "end_bit.npy"), res["end_bit"].astype(np.float64))
 
 
 def _narrow_want(w, sample_bytes, dev, torch):

@@ -18,17 +18,17 @@ except Exception as e: print("ERR", sys.argv[2], e)
 PY
 }
 for i in 1 2; do
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_$i.json 2> $O/bench_driver_$i.err; line $O/bench_driver_$i.json "driver-style $i"
+  timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_$i.json 2> $O/bench_driver_$i.err; line $O/bench_driver_$i.json "driver-style $i"
 done
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; line $O/bench_default.json "default (96 steps)"
-timeout 300 python bench.py --no-cpu-baseline --no-extras --workload config2 --steps 48 > $O/c2.json 2> $O/c2.err; line $O/c2.json "config2"
-timeout 300 python bench.py --no-cpu-baseline --no-extras --workload config4 --steps 48 > $O/c4.json 2> $O/c4.err; line $O/c4.json "config4"
-timeout 300 python bench.py --no-cpu-baseline --no-extras --workload config5 --total-frames 80000 --unique 4096 --shard-of 8 --shard-rank 3 --steps 48 > $O/c5_10k.json 2> $O/c5_10k.err; line $O/c5_10k.json "config5 10k"
-timeout 600 python bench.py --no-cpu-baseline --no-extras --workload config5 --shard-of 8 --shard-rank 3 --steps 24 > $O/c5_share.json 2> $O/c5_share.err; line $O/c5_share.json "config5 125003-frame share"
-timeout 600 python bench.py --gpus 2 --devices 0,0 --backend gloo --steps 20 --warmup 5 --no-extras > $O/bench_2ranks_1gpu.json 2> $O/bench_2ranks_1gpu.err; echo "2-rank rc=$?"; line $O/bench_2ranks_1gpu.json "2 ranks on one GPU (gloo)"
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; line $O/bench_default.json "default (96 steps)"
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras --workload config2 --steps 48 > $O/c2.json 2> $O/c2.err; line $O/c2.json "config2"
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras --workload config4 --steps 48 > $O/c4.json 2> $O/c4.err; line $O/c4.json "config4"
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras --workload config5 --total-frames 80000 --unique 4096 --shard-of 8 --shard-rank 3 --steps 48 > $O/c5_10k.json 2> $O/c5_10k.err; line $O/c5_10k.json "config5 10k"
+timeout 600 python bench.py --full --no-cpu-baseline --no-extras --workload config5 --shard-of 8 --shard-rank 3 --steps 24 > $O/c5_share.json 2> $O/c5_share.err; line $O/c5_share.json "config5 125003-frame share"
+timeout 600 python bench.py --full --gpus 2 --devices 0,0 --backend gloo --steps 20 --warmup 5 --no-extras > $O/bench_2ranks_1gpu.json 2> $O/bench_2ranks_1gpu.err; echo "2-rank rc=$?"; line $O/bench_2ranks_1gpu.json "2 ranks on one GPU (gloo)"
 # the N-rank line's collectives on the hardware that exists: ONE rank, process group through RCCL (init_process_group("nccl", device_id=...), barrier,
 # MAX / SUM all-reduces and the all-gather on device tensors)
-MASTER_ADDR=127.0.0.1 timeout 600 python bench.py --gpus 1 --process-group --backend nccl --steps 20 --warmup 5 --no-extras > $O/bench_rccl_one_rank.json 2> $O/bench_rccl_one_rank.err; echo "rccl one rank rc=$?"; line $O/bench_rccl_one_rank.json "1 rank, RCCL process group"
+MASTER_ADDR=127.0.0.1 timeout 600 python bench.py --full --gpus 1 --process-group --backend nccl --steps 20 --warmup 5 --no-extras > $O/bench_rccl_one_rank.json 2> $O/bench_rccl_one_rank.err; echo "rccl one rank rc=$?"; line $O/bench_rccl_one_rank.json "1 rank, RCCL process group"
 python - $O/bench_rccl_one_rank.json <<'PY'
 import json,sys
 try:

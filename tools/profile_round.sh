@@ -18,7 +18,7 @@ for NAME in $NAMES; do
   esac
   OUT=$REPO/gpurun_out/prof_${ROUND}_$NAME
   mkdir -p "$OUT"
-  BENCH="python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-pipeline $ARGS"
+  BENCH="python $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-pipeline $ARGS"
   echo "== $NAME: kernel trace (one step at a time)"; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $BENCH > "$OUT/trace.log" 2>&1
   grep '"metric"' "$OUT/trace.log" | tail -1 > "$OUT/bench_line.json"
   SETS=("FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR")
@@ -33,7 +33,7 @@ for NAME in $NAMES; do
     echo "== config3: one merged launch of twelve steps at a time"
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/merged12" -o t -- python $REPO/tools/merge_probe.py 12 5 > "$OUT/merged12.log" 2>&1
     echo "== config3: kernel trace of the pipelined steps (the timed mode)"
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/pipe" -o t -- python $REPO/bench.py --steps 48 --warmup 12 --no-cpu-baseline --no-extras > "$OUT/pipe.log" 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/pipe" -o t -- python $REPO/bench.py --full --steps 48 --warmup 12 --no-cpu-baseline --no-extras > "$OUT/pipe.log" 2>&1
     python $REPO/tools/trace_pipelined.py "$OUT/pipe" > "$OUT/pipelined_trace.txt" 2>&1
     for set in "FETCH_SIZE" "WRITE_SIZE"; do
       timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$OUT/merged12_$set" -o p -- python $REPO/tools/merge_probe.py 12 3 > "$OUT/merged12_$set.log" 2>&1

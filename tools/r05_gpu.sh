@@ -46,7 +46,7 @@ pipe)
         c5)  args="--workload config5 --total-frames 80000 --unique 4096 --shard-of 8 --shard-rank 3 --steps 48" ;;
         c4)  args="--workload config4 --steps 48" ;;
       esac
-      timeout 300 python bench.py --no-cpu-baseline --no-extras $args > $O/pipe_$v.$name.$r.json 2> $O/pipe_$v.$name.$r.err
+      timeout 300 python bench.py --full --no-cpu-baseline --no-extras $args > $O/pipe_$v.$name.$r.json 2> $O/pipe_$v.$name.$r.err
       python - "$O/pipe_$v.$name.$r.json" "$v $name r$r" <<'PY' | tee -a $O/pipe.txt
 import json,sys
 try:
@@ -60,7 +60,7 @@ pad)
   v=$1; PADS=$2
   cd $REPO; export CLAXON_HIP_LIB=$(lib $v)
   for r in 1 2; do for p in $PADS; do
-    CLX_LEAN_LDS_PAD=$p timeout 300 python bench.py --no-cpu-baseline --no-extras --steps 48 --warmup 6 > $O/pad_$p.$r.json 2> $O/pad_$p.$r.err
+    CLX_LEAN_LDS_PAD=$p timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps 48 --warmup 6 > $O/pad_$p.$r.json 2> $O/pad_$p.$r.err
     python - "$O/pad_$p.$r.json" "pad $p r$r" <<'PY' | tee -a $O/pad.txt
 import json,sys
 try:

@@ -28,7 +28,7 @@ ab)
         c4)  args="--workload config4 --steps 48" ;;
       esac
       f=$O/ab_${lib}_$pool.$name.$r
-      timeout 300 python bench.py --no-cpu-baseline --no-extras --pool $pool $args > $f.json 2> $f.err
+      timeout 300 python bench.py --full --no-cpu-baseline --no-extras --pool $pool $args > $f.json 2> $f.err
       python - "$f.json" "$lib pool=$pool $name r$r" <<'PY' | tee -a $O/ab.txt
 import json,sys
 try:
@@ -47,7 +47,7 @@ trace)
     lib=${v%%:*}; pool=off; [ "$v" != "${v#*:}" ] && pool=${v#*:}
     if [ "$lib" = head ]; then unset CLAXON_HIP_LIB; else export CLAXON_HIP_LIB=$REPO/claxon_amd/libclaxon_hip_$lib.so; fi
     rm -rf $O/trace_$lib.$pool
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$lib.$pool -o t -- python $REPO/bench.py --steps $STEPS --warmup 12 --no-cpu-baseline --no-extras --repeats 3 --pool $pool > $O/trace_$lib.$pool.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$lib.$pool -o t -- python $REPO/bench.py --full --steps $STEPS --warmup 12 --no-cpu-baseline --no-extras --repeats 3 --pool $pool > $O/trace_$lib.$pool.log 2>&1
     python $REPO/tools/trace_pipelined.py $O/trace_$lib.$pool all > $O/trace_$lib.$pool.$STEPS.txt 2>&1
     rm -rf $O/trace_$lib.$pool
   done ;;

@@ -25,7 +25,7 @@ for r in $(seq 1 $ROUNDS); do for v in $VARS; do
       c4)  args="--workload config4 --steps 48" ;;
     esac
     f=$O/sched_$v.$name.$r
-    timeout 300 python bench.py --no-cpu-baseline --no-extras $args > "$f.json" 2> "$f.err"
+    timeout 300 python bench.py --full --no-cpu-baseline --no-extras $args > "$f.json" 2> "$f.err"
     python - "$f.json" "$v $name r$r" <<'PY' | tee -a $O/sched.txt
 import json,sys
 try:
