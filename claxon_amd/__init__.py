@@ -28,6 +28,8 @@ COMPOSE, NO_COMPOSE = 2048, 4096   # waves composed by content (clx_k_compose) f
 OUT_PCM16 = 8192            # planned batches: the output buffers hold interleaved little-endian 16-bit PCM, written by the decode itself
 POOL = 16384                # pipelined submissions: the scan and the 16-bit tier as clx_k_pool's tickets (round 6's other launch form; off by default)
 OUT_PCM24 = 32768           # the same with packed 24-bit samples (3 bytes each), written by the general lane kernels
+OUT_F32 = 65536             # the same with channel-interleaved float32 normalized to [-1, 1): (float)v * 2^-(bps-1), 4 bytes per sample
+SAMPLE_F32 = 0x104          # sample format of interleave / decode_frames_stream: the floats of OUT_F32 (next to sample_bytes 1..4)
 SUBMIT_DEPTH = 24           # CLX_SUBMIT_DEPTH: the most submissions a Batch keeps in flight (Batch.submit_depth: this batch's)
 
 
@@ -208,6 +210,11 @@ def lib():
 
 def message(msg):
     return lib().clx_message(int(msg)).decode()
+
+
+def _sample_size(sample_bytes):
+    """Bytes per sample of a narrow stage's sample format (1..4, SAMPLE_F32); 0: none."""
+    return 4 if sample_bytes == SAMPLE_F32 else sample_bytes if 1 <= sample_bytes <= 4 else 0
 
 
 def _np_ptr(a):
@@ -521,7 +528,8 @@ class Context:
 
     def decode_frames_stream(self, arena, descs, out_offs, out=None, sample_bytes=0, verify_crc=False, path=0, copy_back=True):
         """clx_decode_frames_stream: host-to-host decode, chunks pipelined (upload | decode | download).  sample_bytes 0: planar
-        int32 (returned as int32 array); 1..4: channel-interleaved little-endian PCM (returned as uint8 array);
+        int32 (returned as int32 array); 1..4: channel-interleaved little-endian PCM (returned as uint8 array); SAMPLE_F32:
+        channel-interleaved normalized floats (returned as float32 array);
         copy_back=False: only the results come back.  Returns (out or None, results)."""
         a = _u8(arena)
         descs = np.ascontiguousarray(descs, dtype=FRAME_DESC_DTYPE)
@@ -529,9 +537,10 @@ class Context:
         n = descs.size
         total = int((out_offs + descs["n_channels"].astype(np.uint64) * descs["block_size"].astype(np.uint64)).max()) if n else 0
         if copy_back and out is None:
-            out = np.zeros(total, dtype=np.int32) if sample_bytes == 0 else np.zeros(total * sample_bytes, dtype=np.uint8)
+            out = (np.zeros(total, dtype=np.int32) if sample_bytes == 0 else np.zeros(total, dtype=np.float32) if sample_bytes == SAMPLE_F32
+                   else np.zeros(total * sample_bytes, dtype=np.uint8))
         if copy_back:
-            assert out.nbytes >= total * (sample_bytes or 4)
+            assert out.nbytes >= total * (_sample_size(sample_bytes) or 4)
         res = np.zeros(n, dtype=FRAME_RESULT_DTYPE)
         st = lib().clx_decode_frames_stream(self._h, _np_ptr(a), a.size, _np_ptr(descs), n, _np_ptr(out) if copy_back else None, sample_bytes,
                                             _np_ptr(out_offs), _np_ptr(res), (VERIFY_CRC16 if verify_crc else 0) | path)
@@ -540,8 +549,9 @@ class Context:
 
     def interleave(self, planar, descs, out_offs, sample_bytes, results=None, pcm=None):
         """One-shot interleave / narrow stage on host arrays: planar i32 -> channel-interleaved little-endian PCM of
-        `sample_bytes` bytes per sample (uint8 array, frame i at byte out_offs[i] * sample_bytes).  Frames whose
-        `results` status is not OK keep whatever `pcm` held."""
+        `sample_bytes` bytes per sample (uint8 array, frame i at byte out_offs[i] * sample_bytes), or with SAMPLE_F32 the
+        normalized floats of OUT_F32 (float32 array, frame i at index out_offs[i]).  Frames whose `results` status is not OK
+        keep whatever `pcm` held."""
         planar = np.ascontiguousarray(planar, dtype=np.int32)
         descs = np.ascontiguousarray(descs, dtype=FRAME_DESC_DTYPE)
         out_offs = np.ascontiguousarray(out_offs, dtype=np.uint64)
@@ -549,8 +559,11 @@ class Context:
         total = int((out_offs + descs["n_channels"].astype(np.uint64) * descs["block_size"].astype(np.uint64)).max()) if n else 0
         assert planar.size >= total
         if pcm is None:
-            pcm = np.zeros(total * sample_bytes, dtype=np.uint8)
-        assert pcm.dtype == np.uint8 and pcm.size >= total * sample_bytes
+            pcm = np.zeros(total, dtype=np.float32) if sample_bytes == SAMPLE_F32 else np.zeros(total * sample_bytes, dtype=np.uint8)
+        if sample_bytes == SAMPLE_F32:
+            assert pcm.dtype == np.float32 and pcm.size >= total
+        else:
+            assert pcm.dtype == np.uint8 and pcm.size >= total * sample_bytes
         if results is not None:
             results = np.ascontiguousarray(results, dtype=FRAME_RESULT_DTYPE)
         st = lib().clx_interleave(self._h, _np_ptr(planar), _np_ptr(descs), n, _np_ptr(out_offs),
@@ -790,3 +803,118 @@ class FlacReader:
             self.close()
         except Exception:
             pass
+
+
+# ---- whole streams to float tensors on the GPU ----------------------------------------------------------------------------------
+
+def _index_stream(ctx, a):
+    """(descs, sample_rate, channels) of a whole FLAC stream held in `a` (uint8): its header, then its frames through the device
+    indexer.  Bytes the indexer cannot chain up (a damaged or truncated frame) become one more descriptor when they start with a
+    valid frame header, so that decoding reports that frame's error as the reference's reader would; a header that does not parse
+    there raises at once."""
+    st, msg, si, off = read_stream_header(a)
+    if st != OK:
+        raise ClaxonError(st, msg)
+    descs, _, stop = ctx.index_frames(a, start=off)
+    if stop < a.size:
+        st, msg, h = parse_frame_header(a[stop:], True)
+        if st != OK:
+            raise ClaxonError(st, msg)
+        tail = np.zeros(1, dtype=FRAME_DESC_DTYPE)
+        tail[0] = (stop, min(a.size - stop, 0xffffffff), h.header_bytes, h.block_size, h.n_channels, h.channel_assignment, h.bps, (0,) * 5)
+        descs = np.concatenate([descs, tail])
+    if descs.size and np.any(descs["bps"] == 0):
+        raise ClaxonError(UNSUPPORTED, 0, "a frame header without bits per sample")
+    return descs, int(si.sample_rate), int(descs["n_channels"][0]) if descs.size else int(si.channels)
+
+
+def _decode_f32(ctx, arena, arena_len, descs, out_offs, out):
+    """One plan (OUT_F32 | VERIFY_CRC16), one run of `arena` (a padded uint8 tensor on the GPU) into the float tensor `out`."""
+    import torch
+    batch = ctx.plan(descs, out_offs, verify_crc=True, path=OUT_F32)
+    try:
+        torch.cuda.current_stream(out.device).synchronize()        # (the uploads and the zero fill go first)
+        batch.run(arena.data_ptr(), int(arena_len), out.data_ptr())
+        return batch.results()
+    finally:
+        batch.close()
+
+
+def _raise_first_failure(res, where=""):
+    bad = np.nonzero(np.asarray(res["status"]) != OK)[0]
+    if bad.size:
+        r = res[int(bad[0])]
+        e = ClaxonError(int(r["status"]), int(r["msg"]))
+        if where:
+            e.args = (e.args[0] + where,)
+        raise e
+
+
+def _arena_on_device(ctx, pieces, total):
+    """The byte strings `pieces` [(offset, uint8 array)] in one arena on the context's GPU, padded as the decoder reads it."""
+    import torch
+    host = np.zeros(((total + 15) // 16) * 16 + 32, dtype=np.uint8)
+    for o, a in pieces:
+        host[o:o + a.size] = a
+    return torch.from_numpy(host).to("cuda:%d" % ctx.device)
+
+
+def load(ctx, data):
+    """A whole FLAC stream to (float32 tensor [T, C] on the context's GPU, sample rate): the header, the frames indexed on the device,
+    one plan with OUT_F32 | VERIFY_CRC16 and one run.  Samples are normalized as torchaudio / libsndfile do: v * 2^-(bps-1), in
+    [-1, 1).  Raises ClaxonError with the first failing frame's status and message (the reference's reader stops there too)."""
+    import torch
+    a = _u8(data)
+    descs, rate, ch = _index_stream(ctx, a)
+    bs = descs["block_size"].astype(np.uint64) * descs["n_channels"].astype(np.uint64)
+    out_offs = np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64) if descs.size else np.zeros(0, dtype=np.uint64)
+    if descs.size and np.any(descs["n_channels"] != ch):
+        raise ClaxonError(FORMAT_ERROR, 0, "the stream's frames differ in their channel count")
+    total = int(bs.sum())
+    out = torch.zeros(total, dtype=torch.float32, device="cuda:%d" % ctx.device)
+    if descs.size:
+        arena = _arena_on_device(ctx, [(0, a)], a.size)
+        res = _decode_f32(ctx, arena, a.size, descs, out_offs, out)
+        _raise_first_failure(res)
+    return out.view(total // max(ch, 1), ch), rate
+
+
+def load_batch(ctx, streams):
+    """Several whole FLAC streams to (float32 tensor [N, T_max, C] on the context's GPU, zero-padded; lengths int64 [N]; sample rates)
+    with one plan and one run: the streams sit in one arena at 16-byte aligned places, every frame reads no further than its own
+    stream's end.  T_max is rounded up to a multiple of 8 so that every block starts on 32 bytes (the float tiers' alignment).
+    Raises ValueError when the streams differ in their channel count, ClaxonError on the first failing frame."""
+    import torch
+    arrs = [_u8(s) for s in streams]
+    idx = [_index_stream(ctx, a) for a in arrs]
+    chans = {c for _, _, c in idx}
+    if len(chans) > 1:
+        raise ValueError("load_batch: the streams differ in their channel count (%s)" % sorted(chans))
+    ch = chans.pop() if chans else 1
+    lengths = [int(d["block_size"].astype(np.int64).sum()) for d, _, _ in idx]
+    t_max = ((max(lengths, default=0) + 7) // 8) * 8
+    pieces, all_descs, all_offs, base = [], [], [], 0
+    for k, (a, (d, _, _)) in enumerate(zip(arrs, idx)):
+        if d.size and np.any(d["n_channels"] != ch):
+            raise ClaxonError(FORMAT_ERROR, 0, "stream %d: its frames differ in their channel count" % k)
+        d = d.copy()
+        end = base + a.size
+        d["byte_off"] += np.uint64(base)
+        d["max_bytes"] = np.minimum(d["max_bytes"].astype(np.uint64), np.uint64(end) - d["byte_off"]).astype(np.uint32)
+        t = np.concatenate([[0], np.cumsum(d["block_size"].astype(np.uint64))[:-1]]).astype(np.uint64) if d.size else np.zeros(0, np.uint64)
+        all_descs.append(d)
+        all_offs.append(np.uint64(k * t_max * ch) + t * np.uint64(ch))
+        pieces.append((base, a))
+        base = ((end + 15) // 16) * 16
+    out = torch.zeros(len(arrs) * t_max * ch, dtype=torch.float32, device="cuda:%d" % ctx.device)
+    descs = np.concatenate(all_descs) if all_descs else np.zeros(0, dtype=FRAME_DESC_DTYPE)
+    if descs.size:
+        out_offs = np.concatenate(all_offs).astype(np.uint64)
+        arena = _arena_on_device(ctx, pieces, base)
+        res = _decode_f32(ctx, arena, base, descs, out_offs, out)
+        first = np.cumsum([0] + [d.size for d in all_descs])
+        bad = np.nonzero(np.asarray(res["status"]) != OK)[0]
+        if bad.size:
+            k = int(np.searchsorted(first, int(bad[0]), side="right")) - 1
+            _raise_first_failure(res, " (stream %d)" % k)
+    return out.view(len(arrs), t_max, ch), torch.tensor(lengths, dtype=torch.int64), [r for _, r, _ in idx]

@@ -578,6 +578,12 @@ int batch_plan_(clx_batch* b, const clx_frame_desc* frames, size_t n, const uint
             if (frames[i].bps > wide) { ctx->last_error = std::string(wide == 16u ? "CLX_OUT_PCM16" : "CLX_OUT_PCM24") + ": frame " + std::to_string(i) + " has more than " + std::to_string(wide) + " bits per sample"; return CLX_API_ERROR; }
         flags |= CLX_PATH_LANES | CLX_LANES_FUSED;
     }
+    if (flags & CLX_OUT_F32) {
+        // normalized float output straight from the decode: every width, the lane kernels' fused build with the float tiers in front
+        if (flags & (CLX_OUT_PCM16 | CLX_OUT_PCM24)) { ctx->last_error = "CLX_OUT_F32 excludes CLX_OUT_PCM16 / CLX_OUT_PCM24"; return CLX_API_ERROR; }
+        if (flags & (CLX_PATH_WAVES | CLX_LANES_SPLIT | CLX_LANES_GENERAL)) { ctx->last_error = "CLX_OUT_F32 runs the fused lane kernels with the lean tiers: not with CLX_PATH_WAVES / CLX_LANES_SPLIT / CLX_LANES_GENERAL"; return CLX_API_ERROR; }
+        flags |= CLX_PATH_LANES | CLX_LANES_FUSED;
+    }
     b->n = n; b->flags = flags;
     b->out_len = 0;
     for (size_t i = 0; i < n; ++i) b->out_len = std::max<uint64_t>(b->out_len, out_sample_offsets[i] + (uint64_t)frames[i].n_channels * frames[i].block_size);
@@ -745,7 +751,7 @@ bool launch_lanes(clx_batch* b, const clx_runs& runs, unsigned n_runs, bool spli
                   int stage_slot = clx_batch::kMaxStreams) {
     const unsigned groups = (unsigned)((b->n_slots + 63) / 64);
     const bool composed = runs.r[0].fkey != nullptr && b->n_windows && b->n_multi;
-    const bool pooled = pool != nullptr && (b->flags & CLX_POOL) && !(b->flags & CLX_OUT_PCM24) && !split && !composed && runs.r[0].taken != nullptr && b->any_bps_le16 && !(b->flags & CLX_LANES_GENERAL);
+    const bool pooled = pool != nullptr && (b->flags & CLX_POOL) && !(b->flags & (CLX_OUT_PCM24 | CLX_OUT_F32)) && !split && !composed && runs.r[0].taken != nullptr && b->any_bps_le16 && !(b->flags & CLX_LANES_GENERAL);
 #ifdef CLX_POOL_SCAN_APART      // (measurement builds: the scan as a kernel of its own in front of a pool of decode tickets only)
     if (pooled && b->n_multi) {
         if (!mark("clx_k_scan")) return false;
@@ -782,7 +788,18 @@ bool launch_lanes(clx_batch* b, const clx_runs& runs, unsigned n_runs, bool spli
         }
         // the 16-bit tier first: it marks the groups it decodes with the run's generation number, the general kernels skip them
         const bool p24 = (b->flags & CLX_OUT_PCM24) != 0;     // (packed 24-bit output is the split tier's, for the batch's 16-bit frames too)
-        if (runs.r[0].taken != nullptr && b->any_bps_le16 && !pooled && !p24) {
+        const bool f32 = (b->flags & CLX_OUT_F32) != 0;       // (float output: the tiers' float builds -- the split tier's always)
+        if (f32 && runs.r[0].taken != nullptr) {
+            if (b->any_bps_le16) {
+                if (!mark("clx_k_lean_f32")) return false;
+                hipLaunchKernelGGL(clx_k_lean_f32, dim3(groups, n_runs), dim3(64), 0, stream, runs,
+                                   (const clx_dev_frame*)b->d_frames, (uint32_t)b->n_slots, b->d_dump);
+            }
+            if (!mark("clx_k_lean24_f32")) return false;
+            hipLaunchKernelGGL(clx_k_lean24_f32, dim3(groups, n_runs), dim3(64), 0, stream, runs,
+                               (const clx_dev_frame*)b->d_frames, (uint32_t)b->n_slots, b->d_dump);
+        }
+        if (runs.r[0].taken != nullptr && b->any_bps_le16 && !pooled && !p24 && !f32) {
             if (!mark("clx_k_lean")) return false;
             // CLX_LEAN_LDS_PAD (measurement builds only): extra dynamic LDS per wave, i.e. fewer decode waves per CU -- the knob behind
             // profiles/r05_occupancy_sweep.txt
@@ -796,7 +813,7 @@ bool launch_lanes(clx_batch* b, const clx_runs& runs, unsigned n_runs, bool spli
         }
         // the split tier for audio of more than 16 bits (launched when the batch holds such frames: it also takes <= 16-bit groups of
         // more than 12 taps that share the batch, which otherwise stay with clx_k_lanes_hi)
-        if (runs.r[0].taken != nullptr && (b->any_bps_gt16 || p24)) {
+        if (runs.r[0].taken != nullptr && (b->any_bps_gt16 || p24) && !f32) {
             if (!mark("clx_k_lean24")) return false;
             hipLaunchKernelGGL(clx_k_lean24, dim3(groups, n_runs), dim3(64), 0, stream, runs,
                                (const clx_dev_frame*)b->d_frames, (uint32_t)b->n_slots, b->d_dump);
@@ -818,7 +835,7 @@ bool launch_lanes(clx_batch* b, const clx_runs& runs, unsigned n_runs, bool spli
         // narrow output: every workgroup of the general kernels decodes into 64 staging rows of its own and narrows them itself
         // (clx_lanes_group) -- the stream's staging, grown here when this launch needs more of it than any before
         clx_runs gruns = runs;
-        if (b->flags & (CLX_OUT_PCM16 | CLX_OUT_PCM24)) {
+        if (b->flags & (CLX_OUT_PCM16 | CLX_OUT_PCM24 | CLX_OUT_F32)) {
             ggrid = std::min(ggrid, std::max(b->stage_groups, 1u));
             const size_t per_run = (size_t)ggrid * 64u * b->stage_stride, need = per_run * n_runs * sizeof(int32_t);
             if (b->stage_cap[stage_slot] < need) {
@@ -869,7 +886,8 @@ clx_run make_run(const clx_batch* b, const clx_batch::Flight& F, const uint8_t* 
     R.slot_frame = composed ? F.d_slot_frame : b->d_slot_frame;
     R.first_slot = composed ? F.d_first_slot : b->d_first_slot;
     R.fkey = composed ? F.d_fkey : nullptr;
-    R.flags = ((b->flags & CLX_VERIFY_CRC16) ? CLX_RUN_CRC : 0u) | ((b->flags & CLX_OUT_PCM16) ? CLX_RUN_PCM16 : 0u) | ((b->flags & CLX_OUT_PCM24) ? CLX_RUN_PCM24 : 0u);
+    R.flags = ((b->flags & CLX_VERIFY_CRC16) ? CLX_RUN_CRC : 0u) | ((b->flags & CLX_OUT_PCM16) ? CLX_RUN_PCM16 : 0u) | ((b->flags & CLX_OUT_PCM24) ? CLX_RUN_PCM24 : 0u) |
+              ((b->flags & CLX_OUT_F32) ? CLX_RUN_F32 : 0u);
     return R;
 }
 void launch_stage1_waves(clx_batch* b, const uint8_t* d_arena, uint64_t alloc_len, int32_t* d_out, clx_sf_desc* d_sfd, clx_frame_result* d_results,
@@ -1315,11 +1333,15 @@ extern "C" int clx_batch_flush(clx_batch* b, void* stream_) {
     return wait_flights(b, stream);
 }
 
+// bytes per sample of a narrow stage's sample format: 1 .. 4, CLX_SAMPLE_F32 (4); 0: not a format
+static uint32_t sample_size(uint32_t sample_bytes) {
+    return sample_bytes == CLX_SAMPLE_F32 ? 4u : (sample_bytes >= 1u && sample_bytes <= 4u) ? sample_bytes : 0u;
+}
 extern "C" int clx_batch_interleave(clx_batch* b, const int32_t* d_planar, void* d_pcm, uint32_t sample_bytes, void* stream_) {
     if (!b || !b->ctx) return CLX_API_ERROR;
     clx_ctx* ctx = b->ctx;
     if (b->n == 0) return CLX_OK;
-    if (!d_planar || !d_pcm || sample_bytes < 1u || sample_bytes > 4u) { ctx->last_error = "clx_batch_interleave: bad argument"; return CLX_API_ERROR; }
+    if (!d_planar || !d_pcm || !sample_size(sample_bytes)) { ctx->last_error = "clx_batch_interleave: bad argument"; return CLX_API_ERROR; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : (b->last_stream ? b->last_stream : ctx->stream);
     if (wait_flights(b, stream) != CLX_OK) return CLX_API_ERROR;       // pipelined submissions still writing d_planar / their results (no-op when none)
@@ -1481,7 +1503,8 @@ extern "C" int clx_decode_frames_stream(clx_ctx* ctx, const uint8_t* arena, size
                                         clx_frame_result* results, uint32_t flags) {
     if (!ctx) return CLX_API_ERROR;
     if (n == 0) return CLX_OK;
-    if (!arena || !frames || !out_sample_offsets || !results || sample_bytes > 4u) { ctx->last_error = "clx_decode_frames_stream: bad argument"; return CLX_API_ERROR; }
+    if (!arena || !frames || !out_sample_offsets || !results || (sample_bytes != 0u && !sample_size(sample_bytes))) { ctx->last_error = "clx_decode_frames_stream: bad argument"; return CLX_API_ERROR; }
+    const uint32_t sbytes = sample_bytes ? sample_size(sample_bytes) : 0u;      // (bytes per sample of the narrow stage's format)
     if (flags & (CLX_ARENA_ON_DEVICE | CLX_OUT_ON_DEVICE)) { ctx->last_error = "clx_decode_frames_stream takes host buffers"; return CLX_API_ERROR; }
     for (size_t i = 1; i < n; ++i)
         if (out_sample_offsets[i] < out_sample_offsets[i - 1] + (uint64_t)frames[i - 1].n_channels * frames[i - 1].block_size) {
@@ -1544,7 +1567,7 @@ extern "C" int clx_decode_frames_stream(clx_ctx* ctx, const uint8_t* arena, size
         const size_t arena_alloc = ((span + 15) & ~(size_t)15) + 48, out_n = (size_t)(o1 - o0);      // (>= 48: the tail cleared below lies inside it also when no frame has a readable byte)
         if (!grow(ctx, &S.d_arena, &S.arena_cap, arena_alloc, "hipMalloc arena") ||
             !grow(ctx, &S.d_out, &S.out_cap, std::max<size_t>(out_n, 1) * sizeof(int32_t), "hipMalloc out") ||
-            (sample_bytes && !grow(ctx, &S.d_pcm, &S.pcm_cap, std::max<size_t>(out_n, 1) * sample_bytes, "hipMalloc pcm"))) { st = CLX_API_ERROR; break; }
+            (sbytes && !grow(ctx, &S.d_pcm, &S.pcm_cap, std::max<size_t>(out_n, 1) * sbytes, "hipMalloc pcm"))) { st = CLX_API_ERROR; break; }
         if (S.res_cap < nc) {
             if (S.h_res) (void)hipHostFree(S.h_res);
             S.h_res = nullptr; S.res_cap = 0;
@@ -1561,14 +1584,14 @@ extern "C" int clx_decode_frames_stream(clx_ctx* ctx, const uint8_t* arena, size
         const bool ok =
             hip_ok(ctx, hipMemsetAsync(S.d_arena + (arena_alloc - 48), 0, 48, S.st), "memset") &&
             hip_ok(ctx, hipMemcpyAsync(S.d_arena, arena + a0, span, hipMemcpyHostToDevice, S.st), "H2D arena") &&
-            (!clear_out || hip_ok(ctx, hipMemsetAsync(sample_bytes ? (void*)S.d_pcm : (void*)S.d_out, 0, out_n * (sample_bytes ? sample_bytes : 4u), S.st), "memset out"));
+            (!clear_out || hip_ok(ctx, hipMemsetAsync(sbytes ? (void*)S.d_pcm : (void*)S.d_out, 0, out_n * (sbytes ? sbytes : 4u), S.st), "memset out"));
         if (!ok) { st = CLX_API_ERROR; break; }
         st = clx_batch_run(S.b, S.d_arena, span, S.d_out, S.st);
         if (st != CLX_OK) break;
         if (sample_bytes) {
             st = clx_batch_interleave(S.b, S.d_out, S.d_pcm, sample_bytes, S.st);
             if (st != CLX_OK) break;
-            if (out && !hip_ok(ctx, hipMemcpyAsync((uint8_t*)out + o0 * sample_bytes, S.d_pcm, out_n * sample_bytes, hipMemcpyDeviceToHost, S.st), "D2H pcm")) { st = CLX_API_ERROR; break; }
+            if (out && !hip_ok(ctx, hipMemcpyAsync((uint8_t*)out + o0 * sbytes, S.d_pcm, out_n * sbytes, hipMemcpyDeviceToHost, S.st), "D2H pcm")) { st = CLX_API_ERROR; break; }
         } else if (out) {
             hipLaunchKernelGGL(clx_k_clear_failed, dim3((unsigned)nc), dim3(256), 0, S.st, S.d_out, (const clx_dev_frame*)S.b->d_frames,
                                (const clx_frame_result*)S.b->d_results, (uint32_t)nc);
@@ -1586,7 +1609,8 @@ extern "C" int clx_interleave(clx_ctx* ctx, const int32_t* planar, const clx_fra
                               void* pcm, uint32_t sample_bytes, uint32_t flags) {
     if (!ctx) return CLX_API_ERROR;
     if (n == 0) return CLX_OK;
-    if (!planar || !frames || !out_sample_offsets || !pcm || sample_bytes < 1u || sample_bytes > 4u) { ctx->last_error = "clx_interleave: bad argument"; return CLX_API_ERROR; }
+    if (!planar || !frames || !out_sample_offsets || !pcm || !sample_size(sample_bytes)) { ctx->last_error = "clx_interleave: bad argument"; return CLX_API_ERROR; }
+    const uint32_t sbytes = sample_size(sample_bytes);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<clx_dev_frame> dev(n);
     uint64_t n_slots = 0;
@@ -1613,16 +1637,16 @@ extern "C" int clx_interleave(clx_ctx* ctx, const int32_t* planar, const clx_fra
     }
     if (ok) {
         if (flags & CLX_PCM_ON_DEVICE) d_pcm = (uint8_t*)pcm;
-        else ok = hip_ok(ctx, hipMalloc((void**)&d_pcm, std::max<uint64_t>(len, 1) * sample_bytes), "hipMalloc pcm") &&
+        else ok = hip_ok(ctx, hipMalloc((void**)&d_pcm, std::max<uint64_t>(len, 1) * sbytes), "hipMalloc pcm") &&
                   // bytes of skipped frames come back as the caller left them
-                  hip_ok(ctx, hipMemcpyAsync(d_pcm, pcm, len * sample_bytes, hipMemcpyHostToDevice, ctx->stream), "H2D pcm");
+                  hip_ok(ctx, hipMemcpyAsync(d_pcm, pcm, len * sbytes, hipMemcpyHostToDevice, ctx->stream), "H2D pcm");
     }
     if (ok) {
         hipLaunchKernelGGL(clx_k_interleave, dim3((unsigned)n), dim3(256), 0, ctx->stream, d_planar, d_frames, d_res, (uint32_t)n, d_pcm, sample_bytes);
         ok = hip_ok(ctx, hipGetLastError(), "clx_k_interleave");
     }
     if (ok && !(flags & CLX_PCM_ON_DEVICE))
-        ok = hip_ok(ctx, hipMemcpyAsync(pcm, d_pcm, len * sample_bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H pcm");
+        ok = hip_ok(ctx, hipMemcpyAsync(pcm, d_pcm, len * sbytes, hipMemcpyDeviceToHost, ctx->stream), "D2H pcm");
     if (ok) ok = hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync");
     cleanup();
     return ok ? CLX_OK : CLX_API_ERROR;

@@ -72,6 +72,7 @@ struct clx_run {
 #define CLX_RUN_CRC 1u
 #define CLX_RUN_PCM16 2u     // `out` holds interleaved 16-bit PCM (claxon_hip.h: CLX_OUT_PCM16)
 #define CLX_RUN_PCM24 4u     // `out` holds interleaved packed 24-bit PCM (CLX_OUT_PCM24)
+#define CLX_RUN_F32 8u       // `out` holds interleaved normalized float32 (CLX_OUT_F32)
 // narrow output: bits 16..31 of the flags = the length of a staging row in units of four samples (>= the batch's largest block size)
 #define CLX_RUN_STAGE_STRIDE(flags) (((flags) >> 16) * 4u)
 #define CLX_RUN_STAGE_BITS(stride) ((((uint32_t)(stride) + 3u) / 4u) << 16)

@@ -1508,6 +1508,10 @@ void clx_k_crc16_runs(const clx_runs runs, const clx_dev_frame* __restrict__ fra
 // MD5 is defined over (metadata.rs:52-53).  Frames that failed to decode are skipped (they expose nothing).
 // One workgroup per frame; HBM-bound: reads 4 B, writes sb B per sample, both coalesced on the common shapes.
 // ------------------------------------------------------------------------------------------------
+// The float output's conversion (CLX_OUT_F32 / CLX_SAMPLE_F32): 2^-(bps-1) for bps = 1 .. 32 -- exact, a power of two -- and a sample's
+// value (float)v * 2^-(bps-1) as the bits of the float
+__device__ __forceinline__ float clx_f32_scale(uint32_t bps) { return __builtin_bit_cast(float, (128u - bps) << 23); }
+__device__ __forceinline__ int32_t clx_f32_bits(int32_t v, float k) { return __builtin_bit_cast(int32_t, static_cast<float>(v) * k); }
 extern "C" __global__ __launch_bounds__(256)
 void clx_k_interleave(const int32_t* __restrict__ planar, const clx_dev_frame* __restrict__ frames,
                       const clx_frame_result* __restrict__ results, uint32_t n_frames,
@@ -1518,6 +1522,18 @@ void clx_k_interleave(const int32_t* __restrict__ planar, const clx_dev_frame* _
     const clx_dev_frame fr = frames[f];
     const uint32_t C = fr.n_channels, bs = fr.block_size;
     const int32_t* __restrict__ src = planar + fr.out_off;
+    if (sb == CLX_SAMPLE_F32) {                        // normalized float32 (CLX_OUT_F32's values): (float)v * 2^-(bps-1)
+        const float k = clx_f32_scale(fr.bps);
+        int32_t* __restrict__ d32 = reinterpret_cast<int32_t*>(dst) + fr.out_off;
+        if (C == 2u && ((uintptr_t)d32 & 7u) == 0u) {  // stereo: one 8-byte store per sample pair
+            int2* d64 = reinterpret_cast<int2*>(d32);
+            for (uint32_t i = threadIdx.x; i < bs; i += 256u) d64[i] = make_int2(clx_f32_bits(src[i], k), clx_f32_bits(src[bs + i], k));
+        } else {
+            for (uint32_t i = threadIdx.x; i < bs; i += 256u)
+                for (uint32_t c = 0; c < C; ++c) d32[i * C + c] = clx_f32_bits(src[c * bs + i], k);
+        }
+        return;
+    }
     uint8_t* __restrict__ d = dst + fr.out_off * (uint64_t)sb;
     const bool even = (fr.out_off & 1ull) == 0ull && ((uintptr_t)dst & 7u) == 0u;
     if (C == 2u && sb == 2u && even) {                 // 16-bit stereo: one dword per sample pair

@@ -1069,6 +1069,13 @@ __device__ __forceinline__ void clx_lanes_run(LaneReader r, Ring& g, uint32_t* r
 // stores): what they wrote is made visible to the lane that narrows it first.  Slow and simple: the odd group the tiers left.
 __device__ __forceinline__ void clx_narrow_row(const clx_run& R, const clx_dev_frame& fr, uint32_t ch, uint32_t n, const int32_t* row, uint32_t narrow) {
     clx_group_fence();
+    if (narrow & CLX_RUN_F32) {          // (float output: (float)v * 2^-(bps-1), one dword per sample -- claxon_hip.h: CLX_OUT_F32)
+        const float k = clx_f32_scale(fr.bps);
+        float* d = reinterpret_cast<float*>(R.out) + fr.out_off + (uint64_t)ch;
+#pragma unroll 1
+        for (uint32_t t = 0; t < n; ++t, d += fr.n_channels) *d = static_cast<float>(row[t]) * k;
+        return;
+    }
     const uint32_t sb = (narrow & CLX_RUN_PCM24) ? 3u : 2u, step = (uint32_t)fr.n_channels * sb;
     uint8_t* d = reinterpret_cast<uint8_t*>(R.out) + (fr.out_off + (uint64_t)ch) * sb;
 #pragma unroll 1
@@ -1093,7 +1100,7 @@ __device__ __forceinline__ void clx_lanes_group(LanesLds& L, const clx_run& R, c
     // samples, re-used for every group the workgroup takes -- and every lane then narrows ITS row into the run's interleaved output
     // (clx_narrow_row).  (Until round 6 every run in flight had a planar scratch as large as the planar output for this, and a
     // kernel of its own behind: ADVICE r05.)
-    const uint32_t narrow = R.flags & (CLX_RUN_PCM16 | CLX_RUN_PCM24);
+    const uint32_t narrow = R.flags & (CLX_RUN_PCM16 | CLX_RUN_PCM24 | CLX_RUN_F32);
     const uint32_t stride = CLX_RUN_STAGE_STRIDE(R.flags);
     int32_t* const out = narrow ? R.planar + (size_t)blockIdx.x * 64u * stride : R.out;
     uint32_t* const errkey = R.errkey;

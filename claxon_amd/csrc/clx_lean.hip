@@ -730,11 +730,60 @@ __device__ __forceinline__ void cln_store_pcm24(const int4* stage0, const LMover
     }
     clx_wave_sync();
 }
+// Float output (CLX_OUT_F32): the rows' samples as (float)v * 2^-(bps-1), bps the row's frame's.  A row's place in the output starts on 32
+// bytes there, so the low five bits of its distance from the base are free: they carry bps - 1 (cln_kernel), and the scale is worked out
+// from what the mover fetches with the place, per store call -- nothing of it stays live across the decode loop.
+__device__ __forceinline__ float cln_f32_scale(uint32_t o) { return __builtin_bit_cast(float, (127u - (o & 31u)) << 23); }      // 2^-(bps-1)
+// Stereo frames: a pair of tiles holds 32 samples of both rows of a frame -- 256 bytes of interleaved floats, two whole 128-byte lines, sixteen
+// 16-byte pieces.  Sixteen adjacent lanes take one frame (lane c: sample pairs 2c, 2c + 1 -- element 2 (c & 1) of piece (c & 7) >> 1 of tile
+// c >> 3 of BOTH rows, read as 8 bytes each), a store instruction covers four frames, eight instructions the pair of tiles (as planar).
+// Mid/side is undone first (M.ms: cln_ms4's step on two samples).  n_tiles: 2, or 1 for a lone last tile (eight pieces).
+__device__ __forceinline__ void cln_store_f32(const int4* stage0, const LMover& M, uint32_t t0, int lane, uint32_t n_tiles) {
+    clx_wave_sync();
+    uint32_t ln = (uint32_t)lane;
+    CLX_OPAQUE(ln);                                                          // (as cln_store_pcm16: nothing of this is kept across the decode loop)
+    const uint32_t c = ln & 15u, fsub = ln >> 4, t = c >> 3, p = (c & 7u) >> 1;
+    // frame F = 4 it + fsub: rows 2F (position 2F + t) and 2F + 1 (position 2F + 1 - t), piece p ^ (F & 3) = p ^ fsub; + 32 int4 per `it`
+    const int2* const s0 = reinterpret_cast<const int2*>(stage0 + t * 256u + (8u * fsub + 4u * t) + (p ^ fsub)) + (c & 1u);
+    const int2* const s1 = reinterpret_cast<const int2*>(stage0 + t * 256u + (8u * fsub + 4u * (1u - t)) + (p ^ fsub)) + (c & 1u);
+#pragma unroll
+    for (uint32_t it = 0; it < 8u; ++it) {
+        int2 a = s0[64u * it], b = s1[64u * it];
+        const uint32_t o = (uint32_t)__shfl((int)M.rowoff, (int)(2u * (4u * it + fsub)), 64);
+        if (M.ms) {                                                          // (left = mid + ((side + 1) >> 1), right = left - side)
+            a.x += (b.x + 1) >> 1; a.y += (b.y + 1) >> 1;
+            b.x = a.x - b.x; b.y = a.y - b.y;
+        }
+        const float k = cln_f32_scale(o);
+        const int4 w = make_int4(clx_f32_bits(a.x, k), clx_f32_bits(b.x, k), clx_f32_bits(a.y, k), clx_f32_bits(b.y, k));
+        if (o != CLN_NO_ROW && c < 8u * n_tiles) clx_store1x16_s(M.base, (o & ~31u) + 8u * t0 + 16u * c, w);      // (a frame's sample t0 sits 8 t0 bytes into its block)
+    }
+    clx_wave_sync();
+}
+// Mono frames: a pair of tiles holds 32 samples of every row -- 128 bytes of floats, the planar mover's shape: eight adjacent lanes write one
+// row's line (lane q: piece q & 3 of tile q >> 2), a store instruction covers eight rows, eight instructions the pair of tiles.
+__device__ __forceinline__ void cln_store_f32_mono(const int4* stage0, const LMover& M, uint32_t t0, int lane, uint32_t n_tiles) {
+    clx_wave_sync();
+    uint32_t ln = (uint32_t)lane;
+    CLX_OPAQUE(ln);
+    const uint32_t q = ln & 7u, h = ln >> 3, t = q >> 2;
+    const int4* const src = stage0 + t * 256u + ((h ^ t) * 4u) + ((q & 3u) ^ ((h >> 1) & 3u));      // row h + 8 i: + 32 int4 per `i`
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; ++i) {
+        const int4 a = src[32u * i];
+        const uint32_t o = (uint32_t)__shfl((int)M.rowoff, (int)(h + 8u * i), 64);
+        const float k = cln_f32_scale(o);
+        const int4 w = make_int4(clx_f32_bits(a.x, k), clx_f32_bits(a.y, k), clx_f32_bits(a.z, k), clx_f32_bits(a.w, k));
+        if (o != CLN_NO_ROW && t < n_tiles) clx_store1x16_s(M.base, (o & ~31u) + 4u * t0 + 16u * q, w);      // (a mono frame's sample t0 sits 4 t0 bytes into its block)
+    }
+    clx_wave_sync();
+}
 // the pair of tiles that starts at sample index t0 (a multiple of 32)
 // (P24: the kernel writes packed 24-bit output too -- clx_k_lean24 alone: in a batch with that output it takes the 16-bit frames as well,
 //  and clx_k_lean's register file has no room for a fourth form of the store)
-template <bool P24>
+template <bool P24, bool F32 = false>
 __device__ __forceinline__ void cln_store_pair(const int4* stage0, const LMover& M, uint32_t t0, int lane) {
+    if constexpr (F32) { if (M.pcm16 == 2u) cln_store_f32_mono(stage0, M, t0, lane, 2u); else cln_store_f32(stage0, M, t0, lane, 2u); return; }
     if (P24 && M.pcm16 == 3u) { cln_store_pcm24(stage0, M, t0, lane, 2u); return; }
     if (M.pcm16 == 2u) { cln_store_pcm16_mono(stage0, M, t0, lane, 2u); return; }
     if (M.pcm16) { cln_store_pcm16(stage0, M, t0, lane, 2u); return; }
@@ -800,8 +849,9 @@ __device__ __forceinline__ void cln_store_pair(const int4* stage0, const LMover&
     clx_wave_sync();
 }
 // a lone tile 0 (the block's last 16 samples when the block size is an odd multiple of 16): 64 bytes x 16 rows per instruction
-template <bool P24>
+template <bool P24, bool F32 = false>
 __device__ __forceinline__ void cln_store_single(const int4* stage0, const LMover& M, uint32_t t0, int lane) {
+    if constexpr (F32) { if (M.pcm16 == 2u) cln_store_f32_mono(stage0, M, t0, lane, 1u); else cln_store_f32(stage0, M, t0, lane, 1u); return; }
     if (P24 && M.pcm16 == 3u) { cln_store_pcm24(stage0, M, t0, lane, 1u); return; }
     if (M.pcm16 == 2u) { cln_store_pcm16_mono(stage0, M, t0, lane, 1u); return; }
     if (M.pcm16) { cln_store_pcm16(stage0, M, t0, lane, 1u); return; }
@@ -838,14 +888,14 @@ struct LTile { uint32_t n; uint32_t t0; };
 __device__ __forceinline__ void cln_done(LTile& T, uint32_t t0) {                 // the tile of sample index t0 is in the stage
     if ((t0 & 16u) == 0u) { T.n = 1u; T.t0 = t0; } else T.n = 2u;
 }
-template <bool P24>
+template <bool P24, bool F32 = false>
 __device__ __forceinline__ void cln_flush(LTile& T, const int4* stage0, const LMover& M, int lane) {
-    if (T.n == 2u) { cln_store_pair<P24>(stage0, M, T.t0, lane); T.n = 0u; }          // (wave-uniform)
+    if (T.n == 2u) { cln_store_pair<P24, F32>(stage0, M, T.t0, lane); T.n = 0u; }     // (wave-uniform)
 }
-template <bool P24>
+template <bool P24, bool F32 = false>
 __device__ __forceinline__ void cln_flush_all(LTile& T, const int4* stage0, const LMover& M, int lane) {
-    if (T.n == 2u) cln_store_pair<P24>(stage0, M, T.t0, lane);
-    else if (T.n == 1u) cln_store_single<P24>(stage0, M, T.t0, lane);
+    if (T.n == 2u) cln_store_pair<P24, F32>(stage0, M, T.t0, lane);
+    else if (T.n == 1u) cln_store_single<P24, F32>(stage0, M, T.t0, lane);
     T.n = 0u;
 }
 
@@ -1102,7 +1152,7 @@ __device__ __forceinline__ int cln_lean_turn(const uint32_t* row, const LRing& g
 #ifndef CLN_SLOW_BUDGET
 #define CLN_SLOW_BUDGET 6u
 #endif
-template <int NP>
+template <int NP, bool F32 = false>
 __device__ __forceinline__ bool cln_body(const clx_buf& buf, LaneReader& r, LRing& g, uint32_t* row, int4* stage, LCur& cur, uint32_t (&H)[2 * NP],
                                          const uint32_t (&C)[NP], uint32_t order, uint32_t shift, int32_t lim, int32_t lim24,
                                          uint32_t per, uint32_t rice2,
@@ -1116,7 +1166,7 @@ __device__ __forceinline__ bool cln_body(const clx_buf& buf, LaneReader& r, LRin
     for (uint32_t t0 = i0; t0 < nmax; t0 += 16u) {
         const bool live = n != 0u && !r.err;
 #ifndef CLN_LAND_FIRST
-        cln_flush<false>(T, stage, M, lane);             // the pair of tiles before, once it is complete
+        cln_flush<false, F32>(T, stage, M, lane);             // the pair of tiles before, once it is complete
 #endif
         int4* const mine = cln_mine(stage, t0, lane);
         if (slow) {
@@ -1140,7 +1190,7 @@ __device__ __forceinline__ bool cln_body(const clx_buf& buf, LaneReader& r, LRin
             CLX_STAT(46, 1);
         }
 #ifdef CLN_LAND_FIRST
-        cln_flush<false>(T, stage, M, lane);             // (measurement: the ring lands in FRONT of the tile stores)
+        cln_flush<false, F32>(T, stage, M, lane);             // (measurement: the ring lands in FRONT of the tile stores)
 #endif
         const bool was_slow = slow;                      // (no lean turn is tried: the history does not fit the packed form)
         int done = 0;
@@ -1214,7 +1264,7 @@ __device__ __forceinline__ bool cln_body(const clx_buf& buf, LaneReader& r, LRin
 }
 
 // LPC / fixed parameters of a lane after the prologue, in the lean kernel's form
-template <int NP>
+template <int NP, bool F32 = false>
 __device__ __forceinline__ bool cln_run(const clx_buf& buf, LaneState<12>& S, LRing& g, uint32_t* row, int4* stage, uint32_t n, uint32_t i0, uint32_t nmax,
                                         const LKind& K, int mode, const Finish& F, const LMover& M, LTile& T, int lane, LCrc& CR, bool crc, bool calm) {
     uint32_t C[NP], H[2 * NP];
@@ -1234,7 +1284,7 @@ __device__ __forceinline__ bool cln_run(const clx_buf& buf, LaneState<12>& S, LR
     // the 24-bit evaluation's range (clx_ltransition), under the same cap for subframes without taps
     const int32_t lim24a = S.order == 0u ? (1 << 29) : S.lim;
     const int32_t lim24 = lim24a < cap ? lim24a : cap;
-    const bool done = cln_body<NP>(buf, S.r, g, row, stage, cur, H, C, S.order, S.shift, lim, lim24, S.per, S.rice2, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
+    const bool done = cln_body<NP, F32>(buf, S.r, g, row, stage, cur, H, C, S.order, S.shift, lim, lim24, S.per, S.rice2, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
     S.r.pos = cur.p; S.k = cur.k; S.pcnt = cur.pcnt; S.next_cnt = cur.next; S.parts_left = cur.parts;
     return done;
 }
@@ -1261,7 +1311,7 @@ __device__ __forceinline__ void cln_unpack12(const uint32_t (&H)[2 * (2 * NP - 1
 
 // The steady state of clx_k_lean24: split turns; the slow turn (as cln_body's) for what they leave -- and for as long as a lane's
 // history is outside the range in which the split evaluation is exact.  Returns false when the wave gives the group up.
-template <int NP, int OMAX>
+template <int NP, int OMAX, bool F32 = false>
 __device__ __forceinline__ bool cln_body24(const clx_buf& buf, LaneReader& r, LRing& g, uint32_t* row, int4* stage, LCur& cur, const int32_t (&hist0)[OMAX],
                                            const uint32_t (&C)[NP], uint32_t order, uint32_t shift, int32_t lim, uint32_t per, uint32_t rice2,
                                            uint32_t n, uint32_t i0, uint32_t nmax, const LKind& K, const Finish& F, const LMover& M, LTile& T, int lane,
@@ -1283,7 +1333,7 @@ __device__ __forceinline__ bool cln_body24(const clx_buf& buf, LaneReader& r, LR
     uint32_t nslow = 0;
     for (uint32_t t0 = i0; t0 < nmax; t0 += 16u) {
         const bool live = n != 0u && !r.err;
-        cln_flush<true>(T, stage, M, lane);              // the pair of tiles before, once it is complete
+        cln_flush<true, F32>(T, stage, M, lane);              // the pair of tiles before, once it is complete
         int4* const mine = cln_mine(stage, t0, lane);
         if (!ring_ok) { cln_reset(buf, g, row, (cur.p - 1u) >> 5, CR, crc); ring_ok = true; }
         else if (cln_pump_now(calm, (t0 & 16u) == 0u)) { cln_land(g, row, CR, crc); cln_request(buf, g, cur.p, !calm || (t0 & 96u) == 0u); }
@@ -1332,7 +1382,7 @@ __device__ __forceinline__ bool cln_body24(const clx_buf& buf, LaneReader& r, LR
     return true;
 }
 
-template <int NP, int OMAX>
+template <int NP, int OMAX, bool F32 = false>
 __device__ __forceinline__ bool cln_run24(const clx_buf& buf, LaneState<OMAX>& S, LRing& g, uint32_t* row, int4* stage, uint32_t n, uint32_t i0, uint32_t nmax,
                                           const LKind& K, const Finish& F, const LMover& M, LTile& T, int lane, LCrc& CR, bool crc, bool calm) {
     static_assert(2 * NP <= OMAX, "taps");
@@ -1347,7 +1397,7 @@ __device__ __forceinline__ bool cln_run24(const clx_buf& buf, LaneState<OMAX>& S
     const int32_t cap = (1 << 29) >> (int)F.wasted;
     const int32_t lim0 = S.order == 0u ? (1 << 29) : S.lim > (1 << 15) ? (1 << 27) : (int32_t)((uint32_t)(S.lim - 1) << 12);
     const int32_t lim = lim0 < cap ? lim0 : cap;
-    const bool done = cln_body24<NP, OMAX>(buf, S.r, g, row, stage, cur, S.hist, C, S.order, S.shift, lim, S.per, S.rice2, n, i0, nmax, K, F, M, T, lane, CR, crc, calm);
+    const bool done = cln_body24<NP, OMAX, F32>(buf, S.r, g, row, stage, cur, S.hist, C, S.order, S.shift, lim, S.per, S.rice2, n, i0, nmax, K, F, M, T, lane, CR, crc, calm);
     S.r.pos = cur.p; S.k = cur.k; S.pcnt = cur.pcnt; S.next_cnt = cur.next; S.parts_left = cur.parts;
     return done;
 }
@@ -1355,7 +1405,8 @@ __device__ __forceinline__ bool cln_run24(const clx_buf& buf, LaneState<OMAX>& S
 // The kernels' common body.  SPLIT = false: clx_k_lean (<= 16-bit audio, <= 12 taps); true: clx_k_lean24 (<= 24-bit audio -- a side
 // channel has 25 --, <= 32 taps, the groups clx_k_lean left).
 // (bx: the group of 64 slots of run R that the wave decodes -- the workgroup's index in clx_k_lean / clx_k_lean24, a decode ticket of clx_k_pool)
-template <bool SPLIT>
+// F32: the float output's build (clx_k_lean_f32 / clx_k_lean24_f32): every run it decodes is CLX_RUN_F32.
+template <bool SPLIT, bool F32 = false>
 __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const clx_dev_frame* __restrict__ frames,
                                            uint32_t n_slots, int32_t* __restrict__ dump_all, uint32_t bx, uint32_t run_idx, int lane) {
     constexpr int OMAX = SPLIT ? 32 : 12;
@@ -1400,7 +1451,8 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
     //      parses, the wave's common block size (a multiple of 16, beyond the prologue), a 16-byte aligned row.
     // (narrow output: `out` holds interleaved 16-bit PCM, a lane's "row" is its FRAME's block there -- both lanes of a pair point to it)
     const bool pcm16 = (R.flags & CLX_RUN_PCM16) != 0u, pcm24 = (R.flags & CLX_RUN_PCM24) != 0u;      // wave-uniform
-    int32_t* const rowp = pcm16 ? reinterpret_cast<int32_t*>(reinterpret_cast<int16_t*>(out) + (active ? fr.out_off : 0ull))
+    // (float output: a lane's row is its FRAME's block of floats, as for 16-bit PCM)
+    int32_t* const rowp = F32 ? out + (active ? fr.out_off : 0ull) : pcm16 ? reinterpret_cast<int32_t*>(reinterpret_cast<int16_t*>(out) + (active ? fr.out_off : 0ull))
                         : pcm24 ? reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(out) + (active ? 3ull * fr.out_off : 0ull))
                                 : out + (active ? fr.out_off + (uint64_t)ch * fr.block_size : 0ull);
     // (where the wave's rows are: the lowest one's address, wave-uniform, and every lane's distance from it -- LMover)
@@ -1410,7 +1462,7 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
         const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(row_lo >> 32), sx, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)row_lo, sx, 64);
         row_lo = other < row_lo ? other : row_lo;
     }
-    const uint64_t row_far = active ? (uint64_t)(uintptr_t)rowp - row_lo + 4ull * bs : 0ull;      // (its last byte's distance, + 1)
+    const uint64_t row_far = active ? (uint64_t)(uintptr_t)rowp - row_lo + (F32 ? 8ull : 4ull) * bs : 0ull;      // (its last byte's distance, + 1)
     bool good = !active;
     SfHead h = { 1u, 0u, 0u, 1u };
     uint32_t bs0 = 0;
@@ -1423,6 +1475,8 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
         good = fr.bps <= (SPLIT ? 24u : 16u) && bs == bs0 && (bs & 15u) == 0u && bs >= (SPLIT ? 64u : 32u) && (((uintptr_t)rowp) & 15u) == 0u && row_far < 0xffffffffull &&
                (!pcm16 || (!SPLIT && ((fr.n_channels == 2u && ch == (slot & 1u)) || fr.n_channels == 1u))) &&       // (narrow output: stereo frames, channel c in lane parity c -- or mono frames)
                (!pcm24 || (SPLIT && fr.n_channels == 2u && ch == (slot & 1u))) &&        // (packed 24-bit output: stereo frames, the split tier -- 16-bit frames too)
+               (!F32 || ((((uintptr_t)rowp) & 31u) == 0u &&                             // (float output: blocks on 32 bytes, stereo frames as for 16-bit PCM --
+                         ((fr.n_channels == 2u && ch == (slot & 1u)) || (!SPLIT && fr.n_channels == 1u)))) &&      //  or mono frames, the 16-bit tier)
                r.pos <= r.limit && (uint64_t)r.origin + 4ull * ((uint64_t)r.limit / 32ull + 16ull) < 0xffffffffull;
         if (good) {
             h = clx_lparse_sf_header(r, clx_channel_bps(fr, ch));
@@ -1431,7 +1485,7 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
     }
     // (narrow output: one kind of frame per wave -- the movers write stereo lines or mono rows)
     const uint32_t nch0 = (uint32_t)__shfl((int)(uint32_t)fr.n_channels, (int)__ffsll((long long)__ballot(active)) - 1, 64);
-    if ((pcm16 || pcm24) && active && fr.n_channels != nch0) good = false;
+    if ((F32 || pcm16 || pcm24) && active && fr.n_channels != nch0) good = false;
     if (!__all(good)) {                                    // clx_k_lanes / clx_k_lanes_hi decode this group
         if (!SPLIT) {
             CLX_STAT(60, 1); CLX_STAT(61, active && (fr.bps > 16u || bs != bs0 || (bs & 15u) != 0u || bs < 32u)); CLX_STAT(62, active && r.err != 0u);
@@ -1488,8 +1542,9 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
     LMover M;
     M.base = ((uint64_t)clx_uniform((uint32_t)(row_lo >> 32)) << 32) | clx_uniform((uint32_t)row_lo);
     M.rowoff = active ? (uint32_t)((uint64_t)(uintptr_t)rowp - row_lo) : CLN_NO_ROW;
+    if constexpr (F32) { if (active) M.rowoff |= (uint32_t)fr.bps - 1u; }      // (the places start on 32 bytes: the low bits carry the scale, cln_f32_scale)
     M.all_real = __all(active);
-    M.pcm16 = pcm24 ? 3u : !pcm16 ? 0u : nch0 == 1u ? 2u : 1u;
+    M.pcm16 = F32 ? (nch0 == 1u ? 2u : 1u) : pcm24 ? 3u : !pcm16 ? 0u : nch0 == 1u ? 2u : 1u;      // (F32: 1 stereo, 2 mono -- cln_store_f32 / _mono)
     (void)dump_all;                                         // (rows that do not exist are not written: no dump slots here)
     Finish F = clx_lfinish_setup(n, h.kind == 0u ? 0u : h.wasted, decor, pair_ok, lane);      // (a constant's wasted bits are folded into it below)
     // every lane in a mid/side pair, no wasted bits (the 16-bit tier; planar or interleaved 16-bit output): the stage takes mid and side as
@@ -1530,7 +1585,7 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
         wild |= cln_ms_wild(s);
         // (the split tier's prologue is up to three tiles long and flushes a pair here; the 16-bit tier's is ONE tile and never does -- the call stays
         //  all the same: round 6's builds without it faulted on the GPU in clx_k_pool, for no reason found in the code)
-        if ((i & 15u) == 0u) cln_flush<SPLIT>(T, stage0, M, lane);
+        if ((i & 15u) == 0u) cln_flush<SPLIT, F32>(T, stage0, M, lane);
         reinterpret_cast<int32_t*>(cln_mine(stage0, i, lane))[(((i >> 2) & 3u) ^ sw) * 4u + (i & 3u)] = clx_lfinish(s, F);
         if ((i & 15u) == 15u) cln_done(T, i & ~15u);
     }
@@ -1555,12 +1610,12 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
         if constexpr (SPLIT) {
             // the split evaluation needs sum|c| < 2^19 (S.lim >= 4096) -- any <= 32 coefficients of <= 15 bits but the all -2^14 row
             if (__any(lv && S.order != 0u && S.lim < 4096)) done = false;
-            else if (omax <= 12u) done = cln_run24<6, OMAX>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, F, M, T, lane, CR, crc, calm);
-            else                  done = cln_run24<16, OMAX>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, F, M, T, lane, CR, crc, calm);
+            else if (omax <= 12u) done = cln_run24<6, OMAX, F32>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, F, M, T, lane, CR, crc, calm);
+            else                  done = cln_run24<16, OMAX, F32>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, F, M, T, lane, CR, crc, calm);
         } else {
-            if (omax <= 4u && mode == 0) done = cln_run<2>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
-            else if (omax <= 8u)         done = cln_run<4>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
-            else                         done = cln_run<6>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
+            if (omax <= 4u && mode == 0) done = cln_run<2, F32>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
+            else if (omax <= 8u)         done = cln_run<4, F32>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
+            else                         done = cln_run<6, F32>(buf, S, g, &L.ring[0][lane], stage0, n, i0, nmax, K, mode, F, M, T, lane, CR, crc, calm);
         }
     }
     if (!done) {                                           // given up: clx_k_lanes decodes the group
@@ -1568,7 +1623,7 @@ __device__ __forceinline__ void cln_kernel(LeanLds& L, const clx_run& R, const c
         CLX_STAT(SPLIT ? 11 : 57, 1);
         return;
     }
-    cln_flush_all<SPLIT>(T, stage0, M, lane);               // what is still in the stage
+    cln_flush_all<SPLIT, F32>(T, stage0, M, lane);               // what is still in the stage
     // ---- trailing parameters of empty partitions are part of the stream (they move the next subframe / the CRC)
     if (n != 0u && !S.r.err && S.transitioned) {
         while (!S.r.err && S.parts_left != 0u) { (void)clx_lread_rice_param(S.r, S.rice2); S.parts_left -= 1u; }
@@ -1682,4 +1737,18 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2
 void clx_k_lean24(const clx_runs runs, const clx_dev_frame* __restrict__ frames, uint32_t n_slots, int32_t* __restrict__ dump_all) {
     __shared__ LeanLds L;
     cln_kernel<true>(L, runs.r[blockIdx.y], frames, n_slots, dump_all, blockIdx.x, blockIdx.y, (int)threadIdx.x);
+}
+
+// The two tiers' builds for float output (CLX_OUT_F32): the same decode, movers that write the rows' samples as normalized floats
+// (cln_store_f32 / cln_store_f32_mono).  Launched instead of clx_k_lean / clx_k_lean24 for such batches -- the split tier always, so
+// that stereo frames of more than 16 bits and 16-bit groups of more than 12 taps do not all fall through to the general kernels.
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CLN_WAVES)))
+void clx_k_lean_f32(const clx_runs runs, const clx_dev_frame* __restrict__ frames, uint32_t n_slots, int32_t* __restrict__ dump_all) {
+    __shared__ LeanLds L;
+    cln_kernel<false, true>(L, runs.r[blockIdx.y], frames, n_slots, dump_all, blockIdx.x, blockIdx.y, (int)threadIdx.x);
+}
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+void clx_k_lean24_f32(const clx_runs runs, const clx_dev_frame* __restrict__ frames, uint32_t n_slots, int32_t* __restrict__ dump_all) {
+    __shared__ LeanLds L;
+    cln_kernel<true, true>(L, runs.r[blockIdx.y], frames, n_slots, dump_all, blockIdx.x, blockIdx.y, (int)threadIdx.x);
 }

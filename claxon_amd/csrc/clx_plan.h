@@ -103,7 +103,8 @@ static inline size_t clx_plan_lanes(const clx_dev_frame* dev, size_t n, uint64_t
 // content hold frames of one block size and width class: the count is the same in stream order.)
 // flags: the batch's (CLX_OUT_PCM16: the 16-bit tier writes narrow output for waves of stereo frames whose channel c sits in a lane of
 // parity c and whose blocks start on 16 bytes of int16, or of mono frames alone; CLX_OUT_PCM24: both tiers, stereo frames whose
-// blocks start on 16 bytes -- everything else is left for certain too).
+// blocks start on 16 bytes; CLX_OUT_F32: the 16-bit tier's stereo or mono frames and the split tier's stereo ones, blocks that start on
+// 32 bytes -- everything else is left for certain too).
 // sure_out (optional): the groups that are left for certain.
 static inline unsigned clx_plan_general_grid(const clx_dev_frame* dev, const uint32_t* slot_frame, uint64_t n_slots, uint32_t flags = 0, uint64_t* sure_out = nullptr) {
     const uint64_t groups = (n_slots + 63) / 64;
@@ -123,6 +124,9 @@ static inline unsigned clx_plan_general_grid(const clx_dev_frame* dev, const uin
                 left = left || d.n_channels != 2u || (d.out_off & 15ull) != 0ull || ((s - d.first_slot) & 1u) != (s & 1u);
             if (flags & CLX_OUT_PCM16)
                 left = left || d.n_channels > 2u || d.n_channels != ch0 || (d.out_off & 7ull) != 0ull || (d.n_channels == 2u && ((s - d.first_slot) & 1u) != (s & 1u));
+            if (flags & CLX_OUT_F32)                         // (float output: as PCM16, blocks that start on 32 bytes, mono frames of <= 16 bits)
+                left = left || d.n_channels > 2u || d.n_channels != ch0 || (d.out_off & 7ull) != 0ull || (d.n_channels == 2u && ((s - d.first_slot) & 1u) != (s & 1u)) ||
+                       (d.n_channels == 1u && d.bps > 16u);
         }
         sure += left ? 1u : 0u;
     }

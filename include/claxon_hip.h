@@ -232,8 +232,24 @@ enum {
      * gives.  Every frame must have at most 24 bits per sample.  The split tier (clx_k_lean24, which takes the batch's 16-bit frames too
      * in this mode) writes a stereo frame's 32 sample pairs as twelve 16-byte pieces from the tiles it stages anyway (blocks that start on 16 bytes: out_sample_offsets[i] a multiple of 16); mono and
      * multi-channel frames, odd block sizes and waves that give up go through the general kernels' staging rows. */
-    CLX_OUT_PCM24       = 1u << 15
+    CLX_OUT_PCM24       = 1u << 15,
+    /* Normalized float output straight from the decode (planned batches: clx_batch_create + clx_batch_run / clx_batch_submit): `d_out`
+     * points to channel-interleaved IEEE float32, addressed as CLX_OUT_PCM16 with 4-byte samples -- frame i's block starts at float
+     * index out_sample_offsets[i], sample t of channel c at + t * n_channels + c (lib.rs:473-520's order).  Sample v of a frame whose
+     * header says `bps` bits becomes (float)v * 2^-(bps-1): round-to-nearest-even int -> float, then an exact power-of-two scale --
+     * in numpy v.astype(np.float32) * np.float32(2.0 ** (1 - bps)).  For every valid stream (|v| < 2^23) the value is exact and lies
+     * in [-1, 1), the convention of torchaudio and libsndfile; out-of-range values (runaway mid/side streams) convert by the same
+     * formula, with no clamping.  Every frame width the decoder takes is allowed.  Excludes CLX_OUT_PCM16 / CLX_OUT_PCM24; refused
+     * with CLX_PATH_WAVES / CLX_LANES_SPLIT / CLX_LANES_GENERAL; CLX_POOL is ignored.  The tiers (clx_k_lean_f32 for waves of
+     * <= 16-bit stereo or mono frames, clx_k_lean24_f32 for stereo frames up to 24 bits and 16-bit ones of more than 12 taps) write
+     * whole lines of floats from the tiles they stage, for blocks that start on 32 bytes (out_sample_offsets[i] a multiple of 8);
+     * the rest -- more channels, odd block sizes, mono frames of more than 16 bits, waves that give up -- goes through the general
+     * kernels' staging rows.  Failed frames' bytes are unspecified. */
+    CLX_OUT_F32         = 1u << 16
 };
+/* Sample format for clx_interleave, clx_batch_interleave and clx_decode_frames_stream, next to sample_bytes 1..4: the floats of
+ * CLX_OUT_F32, 4 bytes per sample, frame i at byte 4 * out_sample_offsets[i]. */
+#define CLX_SAMPLE_F32 0x104u
 
 /* One-shot convenience: plan + run + fetch results.  `out` is planar i32
  * (channel c of frame i at out[out_sample_offsets[i] + c*block_size ...),
