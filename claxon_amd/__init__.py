@@ -96,13 +96,13 @@ EXPORTS = [
     "clx_batch_kernel_ms", "clx_batch_kernel_name", "clx_batch_destroy", "clx_read_stream_header", "clx_read_stream_header_ext",
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
-    "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets",
+    "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -173,6 +173,7 @@ def lib():
     L.clx_batch_interleave.argtypes = [vp, vp, vp, C.c_uint32, vp]
     L.clx_index_frames_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), C.c_uint32]
     L.clx_interleave.argtypes = [vp, vp, vp, sz, vp, vp, vp, C.c_uint32, C.c_uint32]
+    L.clx_md5_streams.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, sz, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -571,6 +572,29 @@ class Context:
         self._check(st)
         return pcm
 
+    def md5_streams(self, samples, sample_format, first, counts, bps):
+        """FLAC audio MD5s (clx_md5_streams) of many streams held on the device, one GPU lane per stream: uint8 [n, 16].  `samples` is a
+        CUDA tensor (the work pending on the current torch stream is waited for first) or a device pointer, holding channel-interleaved
+        samples in `sample_format` (1..4 bytes of little-endian PCM, or SAMPLE_F32); stream k is counts[k] samples from sample index
+        first[k] on, hashed as the low ceil(bps[k] / 8) bytes of each."""
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        bps = np.ascontiguousarray(bps, dtype=np.uint8).reshape(-1)
+        if not (first.size == counts.size == bps.size):
+            raise ValueError("md5_streams: first, counts and bps differ in length")
+        if hasattr(samples, "data_ptr"):
+            import torch
+            if not samples.is_cuda:
+                raise ValueError("md5_streams: samples must be on the GPU")
+            torch.cuda.current_stream(samples.device).synchronize()
+            ptr = samples.data_ptr()
+        else:
+            ptr = int(samples) if samples else None
+        out = np.zeros((first.size, 16), dtype=np.uint8)
+        self._check(lib().clx_md5_streams(self._h, ptr, int(sample_format), _np_ptr(first), _np_ptr(counts), _np_ptr(bps), first.size,
+                                          _np_ptr(out), None))
+        return out
+
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
         a = _u8(arena)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -808,7 +832,7 @@ class FlacReader:
 # ---- whole streams to float tensors on the GPU ----------------------------------------------------------------------------------
 
 def _index_stream(ctx, a):
-    """(descs, sample_rate, channels) of a whole FLAC stream held in `a` (uint8): its header, then its frames through the device
+    """(descs, sample_rate, channels, STREAMINFO) of a whole FLAC stream held in `a` (uint8): its header, then its frames through the device
     indexer.  Bytes the indexer cannot chain up (a damaged or truncated frame) become one more descriptor when they start with a
     valid frame header, so that decoding reports that frame's error as the reference's reader would; a header that does not parse
     there raises at once."""
@@ -825,7 +849,7 @@ def _index_stream(ctx, a):
         descs = np.concatenate([descs, tail])
     if descs.size and np.any(descs["bps"] == 0):
         raise ClaxonError(UNSUPPORTED, 0, "a frame header without bits per sample")
-    return descs, int(si.sample_rate), int(descs["n_channels"][0]) if descs.size else int(si.channels)
+    return descs, int(si.sample_rate), int(descs["n_channels"][0]) if descs.size else int(si.channels), si
 
 
 def _decode_f32(ctx, arena, arena_len, descs, out_offs, out):
@@ -859,13 +883,33 @@ def _arena_on_device(ctx, pieces, total):
     return torch.from_numpy(host).to("cuda:%d" % ctx.device)
 
 
-def load(ctx, data):
+def _stream_problem(si, n_samples, digest):
+    """What STREAMINFO says is wrong with a stream that decoded to `n_samples` samples per channel with MD5 `digest` (None: not
+    computed): (text, md5 checked) -- text None when nothing is."""
+    if int(si.samples) and int(si.samples) != n_samples:
+        return "length mismatch: decoded %d samples per channel, STREAMINFO says %d" % (n_samples, int(si.samples)), False
+    if digest is None:
+        return None, False
+    return (None if bytes(digest) == bytes(si.md5sum) else "MD5 signature mismatch"), True
+
+
+_EMPTY_MD5 = bytes.fromhex("d41d8cd98f00b204e9800998ecf8427e")     # (the MD5 of no samples: nothing to hash on the device)
+
+
+def _md5_set(si):
+    return any(bytes(si.md5sum))
+
+
+def load(ctx, data, verify_md5=False):
     """A whole FLAC stream to (float32 tensor [T, C] on the context's GPU, sample rate): the header, the frames indexed on the device,
     one plan with OUT_F32 | VERIFY_CRC16 and one run.  Samples are normalized as torchaudio / libsndfile do: v * 2^-(bps-1), in
-    [-1, 1).  Raises ClaxonError with the first failing frame's status and message (the reference's reader stops there too)."""
+    [-1, 1).  Raises ClaxonError with the first failing frame's status and message (the reference's reader stops there too).
+    verify_md5: also check the stream against STREAMINFO, as `flac -t` does -- its sample count when it is set, then its MD5 when
+    that is set (not all zero), computed on the device from the float output; a mismatch raises ClaxonError(FORMAT_ERROR).  The MD5
+    of ONE stream runs on one GPU lane, far slower than a host core (README); verify() checks many streams at once."""
     import torch
     a = _u8(data)
-    descs, rate, ch = _index_stream(ctx, a)
+    descs, rate, ch, si = _index_stream(ctx, a)
     bs = descs["block_size"].astype(np.uint64) * descs["n_channels"].astype(np.uint64)
     out_offs = np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64) if descs.size else np.zeros(0, dtype=np.uint64)
     if descs.size and np.any(descs["n_channels"] != ch):
@@ -876,45 +920,136 @@ def load(ctx, data):
         arena = _arena_on_device(ctx, [(0, a)], a.size)
         res = _decode_f32(ctx, arena, a.size, descs, out_offs, out)
         _raise_first_failure(res)
+    if verify_md5:
+        n = total // max(ch, 1)
+        digest = None
+        if _md5_set(si) and not (int(si.samples) and int(si.samples) != n):
+            digest = ctx.md5_streams(out, SAMPLE_F32, [0], [total], [int(si.bits_per_sample)])[0] if total else _EMPTY_MD5
+        why, _ = _stream_problem(si, n, digest)
+        if why:
+            raise ClaxonError(FORMAT_ERROR, 0, why)
     return out.view(total // max(ch, 1), ch), rate
 
 
-def load_batch(ctx, streams):
-    """Several whole FLAC streams to (float32 tensor [N, T_max, C] on the context's GPU, zero-padded; lengths int64 [N]; sample rates)
-    with one plan and one run: the streams sit in one arena at 16-byte aligned places, every frame reads no further than its own
-    stream's end.  T_max is rounded up to a multiple of 8 so that every block starts on 32 bytes (the float tiers' alignment).
-    Raises ValueError when the streams differ in their channel count, ClaxonError on the first failing frame."""
+def _decode_streams(ctx, arrs, all_descs, starts, out_len):
+    """Whole streams `arrs` (uint8; their frames `all_descs`) decoded with one plan and one run into a zeroed float tensor of `out_len`
+    samples, stream k's interleaved samples from index starts[k] on.  The streams sit in one arena at 16-byte aligned places and every
+    frame reads no further than its own stream's end.  Returns (tensor, per-frame results or None, index of each stream's first frame)."""
     import torch
-    arrs = [_u8(s) for s in streams]
-    idx = [_index_stream(ctx, a) for a in arrs]
-    chans = {c for _, _, c in idx}
-    if len(chans) > 1:
-        raise ValueError("load_batch: the streams differ in their channel count (%s)" % sorted(chans))
-    ch = chans.pop() if chans else 1
-    lengths = [int(d["block_size"].astype(np.int64).sum()) for d, _, _ in idx]
-    t_max = ((max(lengths, default=0) + 7) // 8) * 8
-    pieces, all_descs, all_offs, base = [], [], [], 0
-    for k, (a, (d, _, _)) in enumerate(zip(arrs, idx)):
-        if d.size and np.any(d["n_channels"] != ch):
-            raise ClaxonError(FORMAT_ERROR, 0, "stream %d: its frames differ in their channel count" % k)
+    pieces, descs, offs, base = [], [], [], 0
+    for a, d, start in zip(arrs, all_descs, starts):
         d = d.copy()
         end = base + a.size
         d["byte_off"] += np.uint64(base)
         d["max_bytes"] = np.minimum(d["max_bytes"].astype(np.uint64), np.uint64(end) - d["byte_off"]).astype(np.uint32)
-        t = np.concatenate([[0], np.cumsum(d["block_size"].astype(np.uint64))[:-1]]).astype(np.uint64) if d.size else np.zeros(0, np.uint64)
-        all_descs.append(d)
-        all_offs.append(np.uint64(k * t_max * ch) + t * np.uint64(ch))
+        bs = d["block_size"].astype(np.uint64) * d["n_channels"].astype(np.uint64)
+        offs.append(np.uint64(start) + np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64) if d.size else np.zeros(0, np.uint64))
+        descs.append(d)
         pieces.append((base, a))
         base = ((end + 15) // 16) * 16
-    out = torch.zeros(len(arrs) * t_max * ch, dtype=torch.float32, device="cuda:%d" % ctx.device)
-    descs = np.concatenate(all_descs) if all_descs else np.zeros(0, dtype=FRAME_DESC_DTYPE)
-    if descs.size:
-        out_offs = np.concatenate(all_offs).astype(np.uint64)
-        arena = _arena_on_device(ctx, pieces, base)
-        res = _decode_f32(ctx, arena, base, descs, out_offs, out)
-        first = np.cumsum([0] + [d.size for d in all_descs])
+    out = torch.zeros(out_len, dtype=torch.float32, device="cuda:%d" % ctx.device)
+    first = np.cumsum([0] + [d.size for d in descs])
+    descs = np.concatenate(descs) if descs else np.zeros(0, dtype=FRAME_DESC_DTYPE)
+    if not descs.size:
+        return out, None, first
+    arena = _arena_on_device(ctx, pieces, base)
+    return out, _decode_f32(ctx, arena, base, descs, np.concatenate(offs).astype(np.uint64), out), first
+
+
+def load_batch(ctx, streams, verify_md5=False):
+    """Several whole FLAC streams to (float32 tensor [N, T_max, C] on the context's GPU, zero-padded; lengths int64 [N]; sample rates)
+    with one plan and one run: the streams sit in one arena at 16-byte aligned places, every frame reads no further than its own
+    stream's end.  T_max is rounded up to a multiple of 8 so that every block starts on 32 bytes (the float tiers' alignment).
+    Raises ValueError when the streams differ in their channel count, ClaxonError on the first failing frame.  verify_md5: then
+    checks every stream against its STREAMINFO as load(verify_md5=True) does, all MD5s in one call; ClaxonError names the first
+    stream that fails."""
+    import torch
+    arrs = [_u8(s) for s in streams]
+    idx = [_index_stream(ctx, a) for a in arrs]
+    chans = {c for _, _, c, _ in idx}
+    if len(chans) > 1:
+        raise ValueError("load_batch: the streams differ in their channel count (%s)" % sorted(chans))
+    ch = chans.pop() if chans else 1
+    lengths = [int(d["block_size"].astype(np.int64).sum()) for d, _, _, _ in idx]
+    t_max = ((max(lengths, default=0) + 7) // 8) * 8
+    for k, (d, _, _, _) in enumerate(idx):
+        if d.size and np.any(d["n_channels"] != ch):
+            raise ClaxonError(FORMAT_ERROR, 0, "stream %d: its frames differ in their channel count" % k)
+    out, res, first = _decode_streams(ctx, arrs, [d for d, _, _, _ in idx], [k * t_max * ch for k in range(len(arrs))],
+                                      len(arrs) * t_max * ch)
+    if res is not None:
         bad = np.nonzero(np.asarray(res["status"]) != OK)[0]
         if bad.size:
             k = int(np.searchsorted(first, int(bad[0]), side="right")) - 1
             _raise_first_failure(res, " (stream %d)" % k)
-    return out.view(len(arrs), t_max, ch), torch.tensor(lengths, dtype=torch.int64), [r for _, r, _ in idx]
+    if verify_md5:
+        sis = [si for _, _, _, si in idx]
+        todo = [k for k, si in enumerate(sis) if _md5_set(si) and not (int(si.samples) and int(si.samples) != lengths[k])] if out.numel() else []
+        digests = dict(zip(todo, ctx.md5_streams(out, SAMPLE_F32, [k * t_max * ch for k in todo], [lengths[k] * ch for k in todo],
+                                                 [int(sis[k].bits_per_sample) for k in todo]))) if todo else {}
+        for k, si in enumerate(sis):
+            why, _ = _stream_problem(si, lengths[k], digests.get(k, _EMPTY_MD5 if _md5_set(si) and not lengths[k] else None))
+            if why:
+                raise ClaxonError(FORMAT_ERROR, 0, "%s (stream %d)" % (why, k))
+    return out.view(len(arrs), t_max, ch), torch.tensor(lengths, dtype=torch.int64), [r for _, r, _, _ in idx]
+
+
+class Verdict:
+    """verify()'s word on one stream: ok; md5_checked (the MD5 was set and compared); status and message of the first problem (OK and
+    "" when there is none); samples: samples per channel decoded (0 when the stream did not get that far)."""
+    __slots__ = ("ok", "md5_checked", "status", "message", "samples")
+
+    def __init__(self, ok, md5_checked, status, message, samples):
+        self.ok, self.md5_checked, self.status, self.message, self.samples = ok, md5_checked, status, message, samples
+
+    def __repr__(self):
+        return "Verdict(ok=%r, md5_checked=%r, status=%d, message=%r, samples=%d)" % (self.ok, self.md5_checked, self.status, self.message,
+                                                                                     self.samples)
+
+
+def verify(ctx, streams):
+    """The `flac -t` of this library, for a corpus: a Verdict per stream (bytes-like FLAC streams), never raising for a bad stream.  All
+    streams decode with one plan and one run (OUT_F32 | VERIFY_CRC16); each sits contiguously in one flat float buffer at a multiple of
+    8 floats, so the streams may differ in channel count and bit depth.  Then every stream whose STREAMINFO has an MD5 is hashed on the
+    device, all in one clx_md5_streams call.  A verdict names the first problem: a header or frame-index error, the first failing
+    frame's status and message, a sample count other than STREAMINFO's, or "MD5 signature mismatch".
+    The decoded audio of the whole call stays on the device, 4 bytes per sample, until the call returns: pass a corpus in chunks."""
+    verdicts = [None] * len(streams)
+    entries, arrs, all_descs, starts, at = [], [], [], [], 0     # entries: (k, STREAMINFO, samples per channel, samples)
+    for k, s in enumerate(streams):
+        a = _u8(s)
+        try:
+            d, _, ch, si = _index_stream(ctx, a)
+        except ClaxonError as e:
+            verdicts[k] = Verdict(False, False, e.status, e.message, 0)
+            continue
+        total = int((d["block_size"].astype(np.int64) * d["n_channels"].astype(np.int64)).sum())
+        entries.append((k, si, total // max(ch, 1), total))
+        arrs.append(a)
+        all_descs.append(d)
+        starts.append(at)
+        at += ((total + 7) // 8) * 8
+    out, res, first = _decode_streams(ctx, arrs, all_descs, starts, max(at, 1))
+    todo = []
+    for (k, si, n, total), at, f0, f1 in zip(entries, starts, first[:-1], first[1:]):
+        bad = np.nonzero(np.asarray(res["status"][f0:f1]) != OK)[0] if f1 > f0 else []
+        if len(bad):
+            r = res[f0 + int(bad[0])]
+            verdicts[k] = Verdict(False, False, int(r["status"]), message(int(r["msg"])), n)
+        else:
+            why, _ = _stream_problem(si, n, None)
+            if why:
+                verdicts[k] = Verdict(False, False, FORMAT_ERROR, why, n)
+            elif not _md5_set(si):
+                verdicts[k] = Verdict(True, False, OK, "", n)
+            elif not 1 <= int(si.bits_per_sample) <= 24:
+                verdicts[k] = Verdict(False, False, UNSUPPORTED, "the MD5 of more than 24 bits per sample is not checked", n)
+            else:
+                todo.append((k, si, n, total, at))
+    if todo:
+        digests = ctx.md5_streams(out, SAMPLE_F32, [at for _, _, _, _, at in todo], [total for _, _, _, total, _ in todo],
+                                  [int(si.bits_per_sample) for _, si, _, _, _ in todo])
+        for (k, si, n, _, _), dg in zip(todo, digests):
+            why, _ = _stream_problem(si, n, dg)
+            verdicts[k] = Verdict(why is None, True, OK if why is None else FORMAT_ERROR, why or "", n)
+    return verdicts

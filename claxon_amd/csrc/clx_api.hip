@@ -8,6 +8,7 @@
 #include "clx_kernels.hip"
 #include "clx_lanes.hip"
 #include "clx_lean.hip"
+#include "clx_md5.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -1350,6 +1351,35 @@ extern "C" int clx_batch_interleave(clx_batch* b, const int32_t* d_planar, void*
                        (uint8_t*)d_pcm, sample_bytes);
     HIP_TRY(ctx, hipGetLastError());
     return CLX_OK;
+}
+
+extern "C" int clx_md5_streams(clx_ctx* ctx, const void* d_samples, uint32_t sample_format, const uint64_t* first_sample,
+                               const uint64_t* n_samples, const uint8_t* bps, size_t n_streams, uint8_t* digests, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    std::vector<clx_md5_job> jobs;
+    size_t cls[5];
+    const char* why = clx_md5_plan(d_samples, sample_format, first_sample, n_samples, bps, n_streams, digests, jobs, cls);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (n_streams == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    clx_md5_job* d_jobs = nullptr; uint4* d_dig = nullptr;
+    bool ok = hip_ok(ctx, hipMalloc((void**)&d_jobs, n_streams * sizeof(clx_md5_job)), "hipMalloc md5 jobs") &&
+              hip_ok(ctx, hipMalloc((void**)&d_dig, n_streams * sizeof(uint4)), "hipMalloc md5 digests") &&
+              hip_ok(ctx, hipMemcpyAsync(d_jobs, jobs.data(), n_streams * sizeof(clx_md5_job), hipMemcpyHostToDevice, stream), "H2D md5 jobs");
+    for (uint32_t w = 1; ok && w <= 4; ++w) {              // one launch per message width, 64 lanes per workgroup
+        const size_t lo = cls[w - 1], cnt = cls[w] - lo;
+        if (!cnt) continue;
+        hipLaunchKernelGGL(clx_k_md5, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, stream, (const uint8_t*)d_samples,
+                           (const clx_md5_job*)(d_jobs + lo), (uint32_t)cnt, sample_format, w, d_dig);
+        ok = hip_ok(ctx, hipGetLastError(), "clx_k_md5");
+    }
+    if (ok) ok = hip_ok(ctx, hipMemcpyAsync(digests, d_dig, n_streams * 16, hipMemcpyDeviceToHost, stream), "D2H md5 digests") &&
+                 hip_ok(ctx, hipStreamSynchronize(stream), "sync");
+    if (!ok) (void)hipStreamSynchronize(stream);           // (nothing may still use the buffers when they are freed)
+    if (d_jobs) (void)hipFree(d_jobs);
+    if (d_dig) (void)hipFree(d_dig);
+    return ok ? CLX_OK : CLX_API_ERROR;
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

@@ -355,6 +355,19 @@ int  clx_batch_results(clx_batch* b, clx_frame_result* results);
  * (off_i + s*channels + c) * sample_bytes of d_pcm -- channel-interleaved, the order the STREAMINFO MD5 is defined
  * over (metadata.rs:52-53).  Frames whose last run failed are skipped.  Async on `stream`, after clx_batch_run. */
 int  clx_batch_interleave(clx_batch* b, const int32_t* d_planar, void* d_pcm, uint32_t sample_bytes, void* stream);
+/* FLAC audio MD5 (the STREAMINFO signature, metadata.rs:52-53) of many streams in one launch, one GPU lane per stream.  d_samples
+ * is a device buffer of channel-interleaved samples in `sample_format`: 1..4 (little-endian two's-complement PCM of that many bytes)
+ * or CLX_SAMPLE_F32 (floats, scaled back exactly as v = f * 2^(bps-1)).  Stream k is the n_samples[k] samples from sample index
+ * first_sample[k] on (byte first_sample[k] * width); each is hashed as its low ceil(bps[k] / 8) bytes, the FLAC rule, and the 16
+ * bytes of its digest go to digests[16 * k] (host memory).  Which source each output holds:
+ *   CLX_OUT_PCM16 -> 2, CLX_OUT_PCM24 -> 3, CLX_OUT_F32 -> CLX_SAMPLE_F32, clx_batch_interleave(.., sb) -> sb.
+ * Planar i32 output has no source format: interleave it first.  No sample byte past a stream's last is read, at any alignment.
+ * Queued on `stream` (NULL: the context's) after what is already there, e.g. a clx_batch_run; returns when the digests are in
+ * host memory.  CLX_API_ERROR (clx_last_error says why) for a bad format, bps outside 1..32, ceil(bps / 8) wider than the
+ * source's samples, CLX_SAMPLE_F32 with bps > 24, or a null pointer when n_streams > 0; n_streams == 0 succeeds.
+ * One stream hashes at a single lane's rate: the device wins by the number of streams (README: measured rates). */
+int  clx_md5_streams(clx_ctx* ctx, const void* d_samples, uint32_t sample_format, const uint64_t* first_sample,
+                     const uint64_t* n_samples, const uint8_t* bps, size_t n_streams, uint8_t* digests, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
