@@ -740,6 +740,8 @@ unsigned pool_waves(clx_batch* b) {
     b->pool_waves = 12u * (unsigned)cus;
     return b->pool_waves;
 }
+// the device's CUs (asked once, with clx_k_pool's wave count)
+unsigned device_cus(clx_batch* b) { return pool_waves(b) / 12u; }
 // The lane kernels of `n_runs` runs of the batch in one launch each (grid.y = the run): scan (where the later channels of
 // multi-channel frames start), the decode (the lean 16-bit tier, then the general kernels on the groups it left -- or the two-wave
 // build), the per-frame results, the CRC.  The runs' scratch (sf_start, errkey) is expected cleared to 0xff: the host does that when
@@ -838,6 +840,16 @@ bool launch_lanes(clx_batch* b, const clx_runs& runs, unsigned n_runs, bool spli
         clx_runs gruns = runs;
         if (b->flags & (CLX_OUT_PCM16 | CLX_OUT_PCM24 | CLX_OUT_F32)) {
             ggrid = std::min(ggrid, std::max(b->stage_groups, 1u));
+            // ... and, for rows longer than FLAC's subset blocks (4 608 samples), the launch's rows within kStageBudget bytes but never
+            // fewer workgroups than the device has CUs: a group of 65 535-sample blocks takes 16 MiB of rows, and a merged launch of
+            // such groups once held 25 GB (tests/test_gpu_long_blocks.py).  The workgroups loop over the list, so fewer of them only
+            // take longer (profiles/long_block_memory.txt); rows up to 4 608 samples keep the grid above.
+            if (b->stage_stride > 4608u) {
+                constexpr size_t kStageBudget = size_t(512) << 20;
+                const size_t group_bytes = (size_t)64u * b->stage_stride * sizeof(int32_t);
+                const size_t floor_per_run = (device_cus(b) + n_runs - 1u) / n_runs;
+                ggrid = (unsigned)std::min<size_t>(ggrid, std::max<size_t>(floor_per_run, kStageBudget / (group_bytes * n_runs)));
+            }
             const size_t per_run = (size_t)ggrid * 64u * b->stage_stride, need = per_run * n_runs * sizeof(int32_t);
             if (b->stage_cap[stage_slot] < need) {
                 if (b->d_stage[stage_slot]) { (void)hipFree(b->d_stage[stage_slot]); b->d_stage[stage_slot] = nullptr; b->stage_cap[stage_slot] = 0; }      // (waits for what uses it)

@@ -21,7 +21,7 @@ BASE_SEED = 20260925
 class SubframeParams(C.Structure):
     _fields_ = [("type", C.c_int32), ("order", C.c_int32), ("qlp_precision", C.c_int32),
                 ("partition_order", C.c_int32), ("rice_param", C.c_int32), ("force_rice2", C.c_int32),
-                ("wasted", C.c_int32), ("reserved", C.c_int32)]
+                ("wasted", C.c_int32), ("escape", C.c_int32)]
 
 
 class FrameParams(C.Structure):
@@ -60,8 +60,9 @@ def lib():
     return _lib
 
 
-def sf(type=SF_LPC, order=8, precision=12, partition_order=4, rice_param=-1, force_rice2=0, wasted=-1):
-    return SubframeParams(type, order, precision, partition_order, rice_param, force_rice2, wasted, 0)
+def sf(type=SF_LPC, order=8, precision=12, partition_order=4, rice_param=-1, force_rice2=0, wasted=-1, escape=None):
+    """escape: None, or the partition whose residuals are written unencoded behind the escape code (0b1111 / Rice2 0b11111)."""
+    return SubframeParams(type, order, precision, partition_order, rice_param, force_rice2, wasted, 0 if escape is None else escape + 1)
 
 
 class Workload:
@@ -113,12 +114,18 @@ def encode_frames(name, pcm, channels, bs, bps, frame_params, sample_rate=44100)
     pcm = np.ascontiguousarray(pcm, dtype=np.int32)
     n = pcm.shape[0]
     fps = (FrameParams * n)(*frame_params)
+    # (verbatim samples of bps + 1 bits -- a side channel -- take less than the estimate; long unary codes under a small forced
+    #  parameter can take more: the arena then grows until the frames fit)
     cap = int(n * (channels * bs * ((bps + 8) // 8 + 1) + 64) + 64)
-    arena = np.zeros(cap, dtype=np.uint8)
     offs = np.zeros(n, dtype=np.uint64)
     lens = np.zeros(n, dtype=np.uint32)
-    used = lib().synth_encode_frames(pcm.ctypes.data, n, channels, bs, bps, sample_rate, C.addressof(fps),
-                                     arena.ctypes.data, cap, 0, offs.ctypes.data, lens.ctypes.data)
+    while True:
+        arena = np.zeros(cap, dtype=np.uint8)
+        used = lib().synth_encode_frames(pcm.ctypes.data, n, channels, bs, bps, sample_rate, C.addressof(fps),
+                                         arena.ctypes.data, cap, 0, offs.ctypes.data, lens.ctypes.data)
+        if used or cap >= 1 << 32:
+            break
+        cap *= 4
     if used == 0:
         raise RuntimeError("synth arena overflow")
     out_offs = np.arange(n, dtype=np.uint64) * np.uint64(channels * bs)

@@ -61,7 +61,9 @@ typedef struct synth_subframe_params {
     int32_t rice_param;       /* >=0: force this k in every partition; -1: optimal per partition */
     int32_t force_rice2;      /* 1: always 5-bit parameters (method 01) */
     int32_t wasted;           /* -1: auto-detect common trailing zero bits; >=0: force (must divide the data) */
-    int32_t reserved;
+    int32_t escape;           /* 0: none; p + 1: partition p is escape coded (parameter 0b1111 / Rice2 0b11111, a 5-bit width,
+                                 raw two's complement residuals).  A partition order that does not divide the block size and a
+                                 predictor order larger than a partition are written as given: the residual header the decoder rejects */
 } synth_subframe_params;
 
 typedef struct synth_frame_params {
@@ -136,6 +138,16 @@ static int best_rice_param(const int32_t* res, int n, int kmax, uint64_t* bits_o
     return best;
 }
 
+static int bits_signed(const int32_t* res, int n) {   /* the width that holds every residual in two's complement (0: all zero) */
+    int w = 0;
+    for (int i = 0; i < n; i++) {
+        uint32_t m = (uint32_t)(res[i] < 0 ? ~res[i] : res[i]);
+        int need = res[i] == 0 ? 0 : m ? 33 - __builtin_clz(m) : 1;
+        if (need > w) w = need;
+    }
+    return w;
+}
+
 static void write_residual(bitw* w, const int32_t* res /* [bs-order] */, int bs, int order, const synth_subframe_params* p) {
     int porder = p->partition_order;
     int nparts = 1 << porder;
@@ -143,11 +155,17 @@ static void write_residual(bitw* w, const int32_t* res /* [bs-order] */, int bs,
     int* kk = (int*)malloc(sizeof(int) * (size_t)nparts);
     int rice2 = p->force_rice2;
     int start = 0;
+    const int esc = p->escape - 1;                     /* the escape-coded partition, -1: none */
     for (int part = 0; part < nparts; part++) {
         int cnt = (part == 0) ? per - order : per;
+        if (cnt < 0) cnt = 0;                          /* (a predictor order beyond the partition: the decoder stops at the header) */
+        if (start + cnt > bs - order) cnt = bs - order - start > 0 ? bs - order - start : 0;
         int k = p->rice_param >= 0 ? p->rice_param : best_rice_param(res + start, cnt, 30, NULL);
+        if (k > 14 && part != esc) {
+            if (esc >= 0 && !p->force_rice2) k = 14;   /* (an escape in a Rice residual stays 0b1111: its other parameters stay <= 14) */
+            else rice2 = 1;
+        }
         kk[part] = k;
-        if (k > 14) rice2 = 1;
         start += cnt;
     }
     bw_put(w, rice2 ? 1 : 0, 2);
@@ -155,7 +173,17 @@ static void write_residual(bitw* w, const int32_t* res /* [bs-order] */, int bs,
     start = 0;
     for (int part = 0; part < nparts; part++) {
         int cnt = (part == 0) ? per - order : per;
+        if (cnt < 0) cnt = 0;
+        if (start + cnt > bs - order) cnt = bs - order - start > 0 ? bs - order - start : 0;
         int k = kk[part];
+        if (part == esc) {
+            int nb = bits_signed(res + start, cnt);
+            bw_put(w, rice2 ? 31 : 15, rice2 ? 5 : 4);
+            bw_put(w, (uint64_t)nb, 5);
+            for (int i = 0; i < cnt && nb; i++) bw_put(w, (uint64_t)(uint32_t)res[start + i] & ((1ull << nb) - 1), (unsigned)nb);
+            start += cnt;
+            continue;
+        }
         bw_put(w, (uint64_t)k, rice2 ? 5 : 4);
         for (int i = 0; i < cnt; i++) {
             uint32_t u = zigzag(res[start + i]);

@@ -40,3 +40,20 @@ def sample_size(fmt):
 def valid_bps(fmt):
     top = 24 if fmt == cx.SAMPLE_F32 else 8 * fmt
     return [b for b in (1, 5, 8, 9, 12, 16, 17, 20, 24, 25, 31, 32) if b <= top]
+
+
+def streaminfo(bs, ch, bps, samples, md5):
+    """fLaC + a STREAMINFO block (the last metadata block) of min = max block size `bs`, 44.1 kHz, `samples` per channel, `md5`."""
+    si = bytearray(34)
+    si[0:2] = bs.to_bytes(2, "big"); si[2:4] = bs.to_bytes(2, "big")
+    si[10:14] = ((44100 << 12) | ((ch - 1) << 9) | ((bps - 1) << 4) | (samples >> 32)).to_bytes(4, "big")
+    si[14:18] = (samples & 0xffffffff).to_bytes(4, "big")
+    si[18:34] = md5
+    return b"fLaC" + bytes([0x80, 0, 0, 34]) + bytes(si)
+
+
+def stream(w, bs, ch, bps, vals, frames=None):
+    """fLaC + STREAMINFO (sample count and MD5 of the source PCM `vals`) + the workload's frames (or the frame order `frames`)."""
+    order = range(w.n) if frames is None else frames
+    body = b"".join(w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])].tobytes() for i in order)
+    return streaminfo(bs, ch, bps, vals.size // ch, ref_md5(vals, bps)) + body

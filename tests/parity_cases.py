@@ -46,13 +46,23 @@ def check_workload(oracle, backend, w, verify_crc=True):
     assert np.array_equal(res["end_bit"], r["end_bits"])
 
 
-def check_truncations(oracle, backend, n_frames=8, cuts_per_frame=24, seed=1000):
-    """EOF parity: every prefix of a frame must fail (or succeed) exactly as the reference does."""
-    w = synth.small_mixed(n_frames, bs=64, seed_off=seed)
-    e = edge_workload()
-    pick = np.random.default_rng(seed).choice(e.n, size=min(e.n, max(4, n_frames // 2)), replace=False)
-    frames = [w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])] for i in range(w.n)] + \
-             [e.arena[int(e.offs[i]):int(e.offs[i] + e.lens[i])] for i in pick if e.lens[i] < 400]
+def frames_of(w, idx=None):
+    """The bytes of frames `idx` (default: all) of a workload, one array each."""
+    return [w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])].copy() for i in (range(w.n) if idx is None else idx)]
+
+
+def check_truncations(oracle, backend, n_frames=8, cuts_per_frame=24, seed=1000, frames=None):
+    """EOF parity: every prefix of a frame must fail (or succeed) exactly as the reference does.  `frames`: these frames (byte
+    arrays) instead of the default mix; returns the (status, message) pairs seen."""
+    if frames is None:
+        w = synth.small_mixed(n_frames, bs=64, seed_off=seed)
+        e = edge_workload()
+        pick = np.random.default_rng(seed).choice(e.n, size=min(e.n, max(4, n_frames // 2)), replace=False)
+        frames = [w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])] for i in range(w.n)] + \
+                 [e.arena[int(e.offs[i]):int(e.offs[i] + e.lens[i])] for i in pick if e.lens[i] < 400]
+        default = True
+    else:
+        default = False
     seen = set()
     for i, fr in enumerate(frames):
         L = len(fr)
@@ -62,17 +72,20 @@ def check_truncations(oracle, backend, n_frames=8, cuts_per_frame=24, seed=1000)
             if c < 0:
                 continue
             seen.add(assert_same_as_oracle(oracle, backend, fr[:c].copy(), True, "frame %d cut %d/%d" % (i, c, L)))
-    assert (cx.OK, 0) in seen and (cx.IO_ERROR, MSG["CLX_MSG_UNEXPECTED_EOF"]) in seen and (cx.END_OF_STREAM, 0) in seen
+    if default:
+        assert (cx.OK, 0) in seen and (cx.IO_ERROR, MSG["CLX_MSG_UNEXPECTED_EOF"]) in seen and (cx.END_OF_STREAM, 0) in seen
+    return seen
 
 
-def check_bitflips(oracle, backend, n_frames=12, trials=16, seed=2000):
+def check_bitflips(oracle, backend, n_frames=12, trials=16, seed=2000, frames=None):
     """Garbage in, the SAME garbage (or the same error) out: wrapping arithmetic, reserved values, first error in
-    stream order.  CRC checks off on both sides, as under cfg(fuzzing)."""
-    w = synth.small_mixed(n_frames, bs=64, seed_off=seed)
+    stream order.  CRC checks off on both sides, as under cfg(fuzzing).  `frames`: these frames (byte arrays) instead of
+    small_mixed(n_frames)."""
+    if frames is None:
+        frames = frames_of(synth.small_mixed(n_frames, bs=64, seed_off=seed))
     rng = np.random.default_rng(seed)
     seen = set()
-    for i in range(w.n):
-        fr = w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])].copy()
+    for i, fr in enumerate(frames):
         _, _, h = cx.parse_frame_header(fr)
         for trial in range(trials):
             g = fr.copy()
@@ -856,3 +869,245 @@ def ms_mover24_workload():
             fps.append(fp)
         parts.append(S.encode_frames("mid/side %d bits bs%d" % (bits, bs), pcm, 2, bs, bits, fps))
     return S.concat("mid/side for the split tier's movers", parts)
+
+
+def _music(rng, i, bs, bits, loud=1.0):
+    """pcm_music_like scaled to `bits` (stereo; the generator's own seed plus i)."""
+    L, R, g = synth.pcm_music_like(int(rng.integers(0, 1 << 20)) + i, bs)
+    k = loud * (1 << (bits - 16)) if bits >= 16 else loud / (1 << (16 - bits))
+    lim = 1 << (bits - 1)
+    return np.clip(np.rint(L * k), -lim, lim - 1).astype(np.int32), np.clip(np.rint(R * k), -lim, lim - 1).astype(np.int32), g
+
+
+def _max_po(bs, order, cap=15):
+    """The largest partition order <= cap that divides bs and leaves the first partition >= order samples."""
+    po = 0
+    while po < cap and bs % (1 << (po + 1)) == 0 and (bs >> (po + 1)) >= order:
+        po += 1
+    return po
+
+
+def long_block_workload(scale=1, light=False):
+    """Frames beyond 4608 samples, up to FLAC's 65535 (frame.rs:169-275; the 16-bit block-size code), in families laid out as whole
+    waves of 64 subframes: (a) 16-bit stereo of one block size that is a multiple of 16 (65520; the 16-bit tier's), (b) 24-bit
+    stereo of one such size (32768; the split tier's: up to 32 taps, 25-bit side channels), (c) one wave of frames the tiers leave
+    for certain -- 65535 and 40001 samples, 4609, 1 / 3 / 6 / 8 channels, 8 .. 24 bits, partition order 15 on 32768 samples (with
+    order 1 an empty first partition), long unary runs under parameter 0, verbatim and constant subframes, wasted bits -- and (d) 31
+    short stereo frames with one long one among them.  (c) fills 26 slots, so (d) starts inside (c)'s wave: long and short blocks
+    share the last two waves.  `light`: (a) and (b) at 8192 samples, for the selections the simulator
+    runs one after the other.  `scale` > 1 adds families of 4609 .. 65520 samples with other seeds (GPU runs)."""
+    S = synth
+    rng = np.random.default_rng(65535)
+    ws = []
+
+    def family(name, bs, n_frames, channels, bps, make):
+        pcm = np.empty((n_frames, channels, bs), dtype=np.int32)
+        fps = []
+        for i in range(n_frames):
+            chans, fp = make(i)
+            for c in range(channels):
+                pcm[i, c] = chans[c]
+            fps.append(fp)
+        ws.append(S.encode_frames(name, pcm, channels, bs, bps, fps))
+
+    def stereo(bs, bits, omax, assign=None):
+        def mk(i):
+            L, R, g = _music(rng, i, bs, bits)
+            ca = (i % 4) if assign is None else assign
+            if i % 7 == 5:                                              # wasted bits in both channels (every assignment keeps them)
+                L, R = (L >> 3) << 3, (R >> 3) << 3
+            fp = S.FrameParams(ca, i % 2, i * bs if i % 2 else i)
+            for c in range(2):
+                if g.uniform() < 0.75:
+                    o = int(g.integers(1, omax + 1))
+                    fp.sf[c] = S.sf(S.SF_LPC, o, int(g.integers(5, 16)), min(int(g.integers(0, 9)), _max_po(bs, o)), force_rice2=int(g.uniform() < 0.25))
+                else:
+                    o = int(g.integers(0, 5))
+                    fp.sf[c] = S.sf(S.SF_FIXED, o, 0, min(int(g.integers(0, 9)), _max_po(bs, o)), force_rice2=int(g.uniform() < 0.25))
+            return (L, R), fp
+        return mk
+
+    b16, b24 = (8192, 8192) if light else (65520, 32768)
+    family("long 16-bit stereo bs%d" % b16, b16, 32, 2, 16, stereo(b16, 16, 12))                 # (a)
+    family("long 24-bit stereo bs%d" % b24, b24, 32, 2, 24, stereo(b24, 24, 32))                 # (b)
+    # (c) one wave the tiers leave for certain
+    def one(name, bs, channels, bps, ca, kinds, sig=None):
+        lim = 1 << (bps - 1)
+        chans = []
+        for c in range(channels):
+            if sig is not None:
+                chans.append(sig(c))
+                continue
+            L, R, g = _music(rng, c, bs, bps)
+            chans.append(L if c % 2 == 0 else R)
+        fp = S.FrameParams(ca, 0, len(ws))
+        for c, kd in enumerate(kinds):
+            if kd[0] == S.SF_CONSTANT:
+                chans[c] = np.full(bs, int(rng.integers(-lim, lim)), dtype=np.int32)
+            elif kd[0] == S.SF_VERBATIM:
+                chans[c] = rng.integers(-lim, lim, bs).astype(np.int32)
+            fp.sf[c] = S.sf(*kd)
+        ws.append(S.encode_frames(name, np.stack(chans)[None], channels, bs, bps, [fp]))
+    L = S.SF_LPC
+    one("65535 16-bit L/S, 32 taps", 65535, 2, 16, S.CH_LEFT_SIDE, [(L, 32, 15, 0), (L, 12, 14, 0, -1, 1)])
+    one("40001 24-bit M/S", 40001, 2, 24, S.CH_MID_SIDE, [(L, 32, 15, 0), (L, 16, 15, 0, -1, 1)])
+    one("4609 8-bit mono", 4609, 1, 8, 0, [(S.SF_FIXED, 3, 0, 0)])
+    one("4609 12-bit 3 ch", 4609, 3, 12, 0, [(L, 4, 10, 0), (S.SF_VERBATIM, 0, 0, 0), (S.SF_FIXED, 1, 0, 0)])
+    one("8192 20-bit 6 ch", 8192, 6, 20, 0, [(L, 1 + 5 * c, 13, 5) for c in range(6)])
+    one("16384 24-bit 8 ch", 16384, 8, 24, 0, [(L, 8, 15, 6), (S.SF_CONSTANT, 0, 0, 0), (S.SF_VERBATIM, 0, 0, 0), (S.SF_FIXED, 4, 0, 10, -1, 1),
+                                               (L, 32, 15, 9, -1, 0, 2), (L, 2, 6, 13), (S.SF_FIXED, 0, 0, 3), (L, 24, 12, 4)])
+    one("32768 16-bit P15, order 1: an empty first partition", 32768, 2, 16, 0, [(S.SF_FIXED, 1, 0, 15), (L, 1, 12, 15)])
+    spikes = lambda c: np.where(rng.random(16384) < 0.002, rng.integers(-30000, 30000, 16384), rng.integers(-2, 3, 16384)).astype(np.int32)
+    one("16384 16-bit unary runs under k = 0", 16384, 2, 16, 0, [(S.SF_FIXED, 0, 0, 2, 0), (S.SF_FIXED, 1, 0, 0, 0, 1)], sig=spikes)
+    # (d) short frames with one long one among them, in (c)'s wave and the next (a wave's rows are as long as its longest block)
+    for i in range(31):
+        one("4096 beside a long block", 4096, 2, 16, i % 4, [(L, 8, 12, 3), (L, 8, 12, 3)])
+        if i == 17:
+            one("32768 among 4096", 32768, 2, 16, S.CH_MID_SIDE, [(L, 12, 14, 6), (L, 12, 14, 6)])
+    for rep in range(1, scale):
+        for bs in (8192, 16384, 32768, 65520):
+            family("long 16-bit stereo bs%d #%d" % (bs, rep), bs, 32, 2, 16, stereo(bs, 16, 12))
+            family("long 24-bit stereo bs%d #%d" % (bs, rep), bs, 32, 2, 24, stereo(bs, 24, 32))
+        family("4609 16-bit stereo #%d" % rep, 4609, 32, 2, 16, stereo(4609, 16, 12))
+        family("40001 20-bit stereo #%d" % rep, 40001, 8, 2, 20, stereo(40001, 20, 32))
+    return synth.concat("long blocks", ws)
+
+
+ESCAPE_KINDS = {      # kind -> the (status name, message name) the reference gives the frame
+    "ok": ("CLX_OK", None),
+    "escape": ("CLX_UNSUPPORTED", "CLX_MSG_UNENCODED_BINARY"),
+    "bad order": ("CLX_FORMAT_ERROR", "CLX_MSG_INVALID_PARTITION_ORDER"),
+    "bad residual": ("CLX_FORMAT_ERROR", "CLX_MSG_INVALID_RESIDUAL"),
+}
+
+
+def escape_workload():
+    """Escape-coded partitions (parameter 0b1111, Rice2 0b11111: claxon answers "unencoded binary is not yet implemented",
+    subframe.rs:316-319, :358-361) in the first, a middle and the last partition, in channel 0 and in the last channel, under Rice
+    and Rice2; a partition order that does not divide the block size and a predictor order beyond the first partition (the two
+    residual format errors, subframe.rs:262-277); frames whose channel 0 fails one way and whose last channel fails another (the
+    FIRST error in stream order is the frame's).  Every family is a whole wave of good frames of the same shape with the broken ones
+    among them, so the tiers take those waves: 16-bit stereo (the 16-bit tier), 24-bit stereo (the split tier), 16-bit mono under
+    Rice2, and six-channel frames (the general kernels).  (An escape in a Rice residual stays 0b1111: the generator then keeps the
+    other partitions' parameters <= 14 instead of switching the residual to Rice2.)  Returns the workload; `w.kinds[i]` (a key of ESCAPE_KINDS) and
+    `w.places[i]` (where the escape sits: "first" / "middle" / "last", "ch0" / "chN", "rice" / "rice2") describe frame i."""
+    S = synth
+    rng = np.random.default_rng(1515)
+    ws, kinds, places = [], [], []
+    po = 4
+    where = {"first": 0, "middle": 7, "last": 15}
+    plan = [("escape", "first", 0, 0), ("ok",), ("escape", "middle", 0, 1), ("escape", "last", -1, 0), ("ok",), ("escape", "first", -1, 1),
+            ("escape", "last", 0, 1), ("bad order",), ("ok",), ("bad residual",), ("escape", "middle", -1, 0), ("bad order", "escape"),
+            ("escape", "bad residual"), ("ok",), ("escape", "last", -1, 1), ("ok",)]
+
+    def family(name, bs, n_frames, channels, bps, order):
+        pcm = np.empty((n_frames, channels, bs), dtype=np.int32)
+        fps = []
+        for i in range(n_frames):
+            chans = []
+            for c in range(0, channels, 2):
+                L, R, g = _music(rng, i + c, bs, bps)
+                chans += [L, R]
+            chans = chans[:channels]
+            ca = (i % 4) if channels == 2 else 0
+            fp = S.FrameParams(ca, 0, i)
+            rice2 = int(g.uniform() < 0.2)
+            for c in range(channels):
+                fp.sf[c] = S.sf(S.SF_LPC, order, 12, po, force_rice2=rice2)
+            p = plan[(i + len(ws)) % len(plan)]
+            last = channels - 1
+            if p[0] == "escape" and len(p) == 4:
+                c = 0 if p[2] == 0 else last
+                fp.sf[c] = S.sf(S.SF_LPC, order, 12, po, force_rice2=p[3], escape=where[p[1]])
+                kinds.append("escape"); places.append((p[1], "ch0" if c == 0 else "chN", "rice2" if p[3] else "rice"))
+            elif p[0] == "bad order":
+                fp.sf[0] = S.sf(S.SF_LPC, order, 12, 13 if bs == 4096 else 15)            # (4096 = 2^12; 1024, 512 = 2^10, 2^9: no divisor)
+                if len(p) == 2 and last:                                                 # ... and an escape in the last channel behind it
+                    fp.sf[last] = S.sf(S.SF_LPC, order, 12, po, escape=3)
+                kinds.append("bad order"); places.append(None)
+            elif p[0] == "bad residual":
+                fp.sf[last] = S.sf(S.SF_LPC, order, 12, int(np.log2(bs)) - 2)           # four samples per partition, fewer than `order`
+                kinds.append("bad residual"); places.append(None)
+            elif p[0] == "escape":                                                       # an escape in channel 0, a bad residual behind it
+                fp.sf[0] = S.sf(S.SF_LPC, order, 12, po, escape=0)
+                if last:
+                    fp.sf[last] = S.sf(S.SF_LPC, order, 12, int(np.log2(bs)) - 2)
+                kinds.append("escape"); places.append(("first", "ch0", "rice"))
+            else:
+                kinds.append("ok"); places.append(None)
+            for c in range(channels):
+                pcm[i, c] = chans[c]
+            fps.append(fp)
+        ws.append(S.encode_frames(name, pcm, channels, bs, bps, fps))
+
+    family("escapes 16-bit stereo", 4096, 32, 2, 16, 8)
+    family("escapes 24-bit stereo", 1024, 32, 2, 24, 16)
+    family("escapes 16-bit mono", 512, 64, 1, 16, 8)
+    family("escapes 6 channels", 1024, 16, 6, 16, 8)
+    family("escapes 16-bit stereo, again", 4096, 32, 2, 16, 12)
+    w = synth.concat("escapes", ws)
+    w.kinds, w.places = kinds, places
+    return w
+
+
+def check_against_oracle(oracle, backend, w, arena=None, out="planar", verify_crc=True):
+    """Any workload, intact or not, against the oracle: status and message of every frame; end bit and samples of every OK frame --
+    planar i32, or the interleaved bytes of `out` = "pcm16" / "pcm24" / "f32" (backend.path must carry the matching CLX_OUT_* flag).
+    Returns (statuses, messages) as numpy arrays."""
+    arena = w.arena if arena is None else arena
+    descs, _ = cx.descs_from_offsets(w.arena[:w.arena_len], w.offs, w.lens, check_crc=False)
+    got, res = backend.decode(arena, w.arena_len, descs, w.out_offs, verify_crc, fill=0x11)
+    ref = np.zeros(w.pcm.size, dtype=np.int32)
+    r = oracle.decode_batch(arena[:w.arena_len], w.offs, w.lens, out=ref, out_offs=w.out_offs, check_crc=verify_crc)
+    st, ms = np.asarray(res["status"]), np.asarray(res["msg"])
+    bad = np.nonzero((st != r["statuses"]) | (ms != r["msgs"]))[0]
+    assert bad.size == 0, [(int(i), int(w.block_sizes[i]), int(st[i]), MSG_NAME[int(ms[i])], int(r["statuses"][i]), MSG_NAME[int(r["msgs"][i])]) for i in bad[:6]]
+    ok_frames = np.nonzero(st == cx.OK)[0]
+    assert np.array_equal(np.asarray(res["end_bit"])[ok_frames], r["end_bits"][ok_frames])     # (a failed frame's end bit is not defined)
+    got = np.asarray(got)
+    for i in np.nonzero(st == cx.OK)[0]:
+        a, c, bs = int(w.out_offs[i]), int(w.channels[i]), int(w.block_sizes[i])
+        v = ref[a:a + c * bs]
+        inter = v.reshape(c, bs).T.reshape(-1)
+        if out == "planar":
+            ok = np.array_equal(got[a:a + c * bs], v)
+        elif out == "pcm16":
+            ok = np.array_equal(got.view(np.int16)[a:a + c * bs], inter.astype(np.int16))
+        elif out == "pcm24":
+            u = inter.astype(np.int32).view(np.uint32)
+            ok = np.array_equal(got.view(np.uint8)[3 * a:3 * (a + c * bs)], np.stack([u & 0xff, (u >> 8) & 0xff, (u >> 16) & 0xff], axis=1).astype(np.uint8).reshape(-1))
+        else:
+            want = inter.astype(np.float32) * np.float32(2.0 ** (1 - int(w.bps[i])))
+            ok = np.array_equal(got.view(np.float32)[a:a + c * bs].view(np.uint32), want.view(np.uint32))
+        assert ok, "frame %d (%d ch, bs %d, %d bits, %s)" % (int(i), c, bs, int(w.bps[i]), out)
+    return st, ms
+
+
+def check_escape_kinds(w, st, ms):
+    """Every frame of escape_workload reported what the reference reports (ESCAPE_KINDS), and every placement of an escape was met."""
+    from claxon_msgs import STATUS
+    for i, k in enumerate(w.kinds):
+        s, m = ESCAPE_KINDS[k]
+        assert (int(st[i]), int(ms[i])) == (STATUS[s], MSG[m] if m else 0), (i, k, w.places[i], int(st[i]), MSG_NAME[int(ms[i])])
+    placed = {p for p, k, s in zip(w.places, w.kinds, st) if p and k == "escape" and int(s) == cx.UNSUPPORTED}
+    assert len(placed) >= 10, placed
+
+
+def subset(w, idx):
+    """The frames `idx` of a workload as a workload of their own (bytes copied, outputs back to back)."""
+    parts = []
+    for i in idx:
+        i = int(i)
+        a, n = int(w.out_offs[i]), int(w.channels[i]) * int(w.block_sizes[i])
+        fr = w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])]
+        parts.append(synth.Workload("frame %d" % i, synth._pad_arena(fr, fr.size), [0], [int(w.lens[i])], [w.channels[i]], [w.block_sizes[i]],
+                                    [w.bps[i]], [w.assignments[i]], w.pcm[a:a + n], [0]))
+    out = synth.concat("%s (%d frames)" % (w.name, len(parts)), parts)
+    if hasattr(w, "kinds"):
+        out.kinds, out.places = [w.kinds[int(i)] for i in idx], [w.places[int(i)] for i in idx]
+    return out
+
+
+def for_output(w, out):
+    """The frames of `w` that an output mode takes: CLX_OUT_PCM16 refuses frames of more than 16 bits at plan time."""
+    return subset(w, np.nonzero(w.bps <= 16)[0]) if out == "pcm16" else w

@@ -39,22 +39,6 @@ def _frames(rng, n, ch, bs, bps):
     return synth.encode_frames("md5", frames, ch, bs, bps, fp), pcm.T.reshape(-1)
 
 
-def _streaminfo(bs, ch, bps, samples, md5):
-    si = bytearray(34)
-    si[0:2] = bs.to_bytes(2, "big"); si[2:4] = bs.to_bytes(2, "big")
-    si[10:14] = ((44100 << 12) | ((ch - 1) << 9) | ((bps - 1) << 4) | (samples >> 32)).to_bytes(4, "big")
-    si[14:18] = (samples & 0xffffffff).to_bytes(4, "big")
-    si[18:34] = md5
-    return b"fLaC" + bytes([0x80, 0, 0, 34]) + bytes(si)
-
-
-def _stream(w, bs, ch, bps, vals, frames=None):
-    """fLaC + STREAMINFO (sample count and MD5 of the source PCM `vals`) + the workload's frames (or the frame order `frames`)."""
-    order = range(w.n) if frames is None else frames
-    body = b"".join(w.arena[int(w.offs[i]):int(w.offs[i] + w.lens[i])].tobytes() for i in order)
-    return _streaminfo(bs, ch, bps, vals.size // ch, mc.ref_md5(vals, bps)) + body
-
-
 @pytest.fixture(scope="module")
 def corpus():
     """A few hundred streams: 8..24 bits, mono / stereo / 6 channels, 1..5 frames of 256..4096 samples."""
@@ -66,7 +50,7 @@ def corpus():
         bs = (256, 1024, 576, 4096)[(k // 15) % 4]
         n = 1 + int(rng.integers(0, 5))
         w, vals = _frames(rng, n, ch, bs, bps)
-        out.append(dict(w=w, vals=vals, bps=bps, ch=ch, bs=bs, data=_stream(w, bs, ch, bps, vals)))
+        out.append(dict(w=w, vals=vals, bps=bps, ch=ch, bs=bs, data=mc.stream(w, bs, ch, bps, vals)))
     return out
 
 
@@ -142,9 +126,9 @@ def _damaged(rng):
     """(good stream, frames 2 and 3 swapped, cut after frame 3 of 6): every frame of each passes its CRC-16."""
     bs, ch, bps = 1024, 2, 16
     w, vals = _frames(rng, 6, ch, bs, bps)
-    good = _stream(w, bs, ch, bps, vals)
-    swapped = _stream(w, bs, ch, bps, vals, frames=[0, 1, 3, 2, 4, 5])
-    cut = _stream(w, bs, ch, bps, vals, frames=[0, 1, 2, 3])
+    good = mc.stream(w, bs, ch, bps, vals)
+    swapped = mc.stream(w, bs, ch, bps, vals, frames=[0, 1, 3, 2, 4, 5])
+    cut = mc.stream(w, bs, ch, bps, vals, frames=[0, 1, 2, 3])
     return good, swapped, cut
 
 
