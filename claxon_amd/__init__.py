@@ -96,13 +96,13 @@ EXPORTS = [
     "clx_batch_kernel_ms", "clx_batch_kernel_name", "clx_batch_destroy", "clx_read_stream_header", "clx_read_stream_header_ext",
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
-    "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams",
+    "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -172,6 +172,7 @@ def lib():
     L.clx_batch_results.argtypes = [vp, vp]
     L.clx_batch_interleave.argtypes = [vp, vp, vp, C.c_uint32, vp]
     L.clx_index_frames_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), C.c_uint32]
+    L.clx_index_streams_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, C.POINTER(sz), C.c_uint32]
     L.clx_interleave.argtypes = [vp, vp, vp, sz, vp, vp, vp, C.c_uint32, C.c_uint32]
     L.clx_md5_streams.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, sz, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
@@ -507,6 +508,44 @@ class Context:
         self._check(st)
         return descs[:n.value].copy(), hdrs[:n.value].copy(), int(stop.value)
 
+    def index_streams(self, arena, offs, lens, starts=None, cap=None):
+        """The device indexer for a whole shard (clx_index_streams_device): the streams arena[offs[k] : offs[k] + lens[k]] (offs multiples
+        of 16, ascending), each indexed from offs[k] + starts[k] on, in one pass.  `arena` is bytes-like / numpy (a host arena, uploaded
+        once) or a CUDA uint8 tensor (16-byte aligned, padded like a decode arena; the work pending on the current torch stream is
+        waited for first).  Returns (descs, headers, first_frame, stop_offs): stream k's frames are descs[first_frame[k]:first_frame[k + 1]],
+        exactly the host indexer's answer for that stream alone with byte_off and stop_offs[k] rebased onto the arena."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+        if starts is not None:
+            starts = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        if offs.size != lens.size or (starts is not None and starts.size != offs.size):
+            raise ValueError("index_streams: offs, lens and starts differ in length")
+        flags = 0
+        if hasattr(arena, "data_ptr"):
+            import torch
+            if not arena.is_cuda:
+                raise ValueError("index_streams: a tensor arena must be on the GPU")
+            torch.cuda.current_stream(arena.device).synchronize()
+            ptr, size, flags = arena.data_ptr(), arena.numel() * arena.element_size(), ARENA_ON_DEVICE
+        else:
+            a = _u8(arena)
+            ptr, size = _np_ptr(a), a.size
+        n = offs.size
+        first = np.zeros(n + 1, dtype=np.uint64)
+        stops = np.zeros(n, dtype=np.uint64)
+        found = C.c_size_t(0)
+        cap = int(cap) if cap is not None else int(lens.sum()) // 512 + 4 * n + 64
+        while True:
+            descs = np.zeros(max(cap, 1), dtype=FRAME_DESC_DTYPE)
+            hdrs = np.zeros(max(cap, 1), dtype=FRAME_HEADER_DTYPE)
+            st = lib().clx_index_streams_device(self._h, ptr, size, _np_ptr(offs), _np_ptr(lens), _np_ptr(starts), n, _np_ptr(descs),
+                                                _np_ptr(hdrs), cap, _np_ptr(first), _np_ptr(stops), C.byref(found), flags)
+            if st == API_ERROR and found.value > cap:           # told how many frames there are: once more with room for them
+                cap = int(found.value)
+                continue
+            self._check(st)
+            return descs[:found.value].copy(), hdrs[:found.value].copy(), first, stops
+
     def decode_frames(self, arena, descs, out_offs, out=None, verify_crc=False, path=0):
         """One-shot host->device->host decode.  Returns (out int32, results np FRAME_RESULT_DTYPE)."""
         a = _u8(arena)
@@ -831,25 +870,67 @@ class FlacReader:
 
 # ---- whole streams to float tensors on the GPU ----------------------------------------------------------------------------------
 
-def _index_stream(ctx, a):
-    """(descs, sample_rate, channels, STREAMINFO) of a whole FLAC stream held in `a` (uint8): its header, then its frames through the device
-    indexer.  Bytes the indexer cannot chain up (a damaged or truncated frame) become one more descriptor when they start with a
-    valid frame header, so that decoding reports that frame's error as the reference's reader would; a header that does not parse
-    there raises at once."""
-    st, msg, si, off = read_stream_header(a)
-    if st != OK:
-        raise ClaxonError(st, msg)
-    descs, _, stop = ctx.index_frames(a, start=off)
-    if stop < a.size:
-        st, msg, h = parse_frame_header(a[stop:], True)
+INDEX_CALL_BYTES = (1 << 32) - 64       # clx_index_streams_device takes an arena below 4 GiB per call
+
+
+def _index_arena(ctx, arena, offs, lens, starts, limit=INDEX_CALL_BYTES):
+    """Context.index_streams over the device arena `arena`: (descs, first_frame, stop_offs).  One call, unless the streams span more
+    than a call takes (`limit` bytes): then one call per run of streams that fits, each on its own slice of the tensor, the answers
+    rebased and joined.  (A single stream beyond the limit is refused by the call.)"""
+    n = len(offs)
+    if n == 0 or offs[-1] + lens[-1] <= limit:
+        d, _, first, stops = ctx.index_streams(arena, offs, lens, starts)
+        return d, first, stops
+    descs, first, stops, j = [], [0], [], 0
+    while j < n:
+        g0, e = offs[j], j + 1
+        while e < n and offs[e] + lens[e] - g0 <= limit:
+            e += 1
+        sub = arena[g0:min(((offs[e - 1] + lens[e - 1] + 15) // 16) * 16 + 32, arena.numel())]
+        d, _, f, s = ctx.index_streams(sub, [o - g0 for o in offs[j:e]], lens[j:e], starts[j:e])
+        d["byte_off"] += np.uint64(g0)
+        descs.append(d)
+        first.extend((f[1:].astype(np.int64) + first[-1]).tolist())
+        stops.extend((s.astype(np.int64) + g0).tolist())
+        j = e
+    return np.concatenate(descs), np.array(first, dtype=np.uint64), np.array(stops, dtype=np.uint64)
+
+
+def _index_streams(ctx, arrs):
+    """Whole FLAC streams `arrs` (uint8) made ready to decode: their headers parsed on the host, the streams whose header parses laid
+    out in one arena at 16-byte aligned places, that arena uploaded once and indexed with one Context.index_streams call.  Returns
+    (arena tensor | None, arena length, entries): entries[k] is (descs, sample_rate, channels, STREAMINFO) -- the descriptors address
+    the arena and read no further than the stream's own end -- or the ClaxonError that stream raises.  Bytes the indexer cannot chain
+    up (a damaged or truncated frame) become one more descriptor when they start with a valid frame header, so that decoding reports
+    that frame's error as the reference's reader would; a header that does not parse there is the stream's error."""
+    entries, live, offs, starts, infos, base = [None] * len(arrs), [], [], [], [], 0
+    for k, a in enumerate(arrs):
+        st, msg, si, off = read_stream_header(a)
         if st != OK:
-            raise ClaxonError(st, msg)
-        tail = np.zeros(1, dtype=FRAME_DESC_DTYPE)
-        tail[0] = (stop, min(a.size - stop, 0xffffffff), h.header_bytes, h.block_size, h.n_channels, h.channel_assignment, h.bps, (0,) * 5)
-        descs = np.concatenate([descs, tail])
-    if descs.size and np.any(descs["bps"] == 0):
-        raise ClaxonError(UNSUPPORTED, 0, "a frame header without bits per sample")
-    return descs, int(si.sample_rate), int(descs["n_channels"][0]) if descs.size else int(si.channels), si
+            entries[k] = ClaxonError(st, msg)
+            continue
+        live.append(k); offs.append(base); starts.append(off); infos.append(si)
+        base = ((base + a.size + 15) // 16) * 16
+    if not live:
+        return None, 0, entries
+    arena = _arena_on_device(ctx, [(o, arrs[k]) for o, k in zip(offs, live)], base)
+    descs, first, stops = _index_arena(ctx, arena, offs, [arrs[k].size for k in live], starts)
+    for j, k in enumerate(live):
+        a, si = arrs[k], infos[j]
+        d, stop, end = descs[int(first[j]):int(first[j + 1])], int(stops[j]), offs[j] + a.size
+        if stop < end:
+            st, msg, h = parse_frame_header(a[stop - offs[j]:], True)
+            if st != OK:
+                entries[k] = ClaxonError(st, msg)
+                continue
+            tail = np.zeros(1, dtype=FRAME_DESC_DTYPE)
+            tail[0] = (stop, min(end - stop, 0xffffffff), h.header_bytes, h.block_size, h.n_channels, h.channel_assignment, h.bps, (0,) * 5)
+            d = np.concatenate([d, tail])
+        if d.size and np.any(d["bps"] == 0):
+            entries[k] = ClaxonError(UNSUPPORTED, 0, "a frame header without bits per sample")
+            continue
+        entries[k] = (d, int(si.sample_rate), int(d["n_channels"][0]) if d.size else int(si.channels), si)
+    return arena, base, entries
 
 
 def _decode_f32(ctx, arena, arena_len, descs, out_offs, out):
@@ -901,15 +982,19 @@ def _md5_set(si):
 
 
 def load(ctx, data, verify_md5=False):
-    """A whole FLAC stream to (float32 tensor [T, C] on the context's GPU, sample rate): the header, the frames indexed on the device,
-    one plan with OUT_F32 | VERIFY_CRC16 and one run.  Samples are normalized as torchaudio / libsndfile do: v * 2^-(bps-1), in
+    """A whole FLAC stream to (float32 tensor [T, C] on the context's GPU, sample rate): the header, one upload, the frames indexed on the
+    device from that upload (Context.index_streams), one plan with OUT_F32 | VERIFY_CRC16 and one run.  A stream of 4 GiB or more is
+    refused by the indexer (ClaxonError(API_ERROR)).  Samples are normalized as torchaudio / libsndfile do: v * 2^-(bps-1), in
     [-1, 1).  Raises ClaxonError with the first failing frame's status and message (the reference's reader stops there too).
     verify_md5: also check the stream against STREAMINFO, as `flac -t` does -- its sample count when it is set, then its MD5 when
     that is set (not all zero), computed on the device from the float output; a mismatch raises ClaxonError(FORMAT_ERROR).  The MD5
     of ONE stream runs on one GPU lane, far slower than a host core (README); verify() checks many streams at once."""
     import torch
     a = _u8(data)
-    descs, rate, ch, si = _index_stream(ctx, a)
+    arena, arena_len, entries = _index_streams(ctx, [a])
+    if isinstance(entries[0], ClaxonError):
+        raise entries[0]
+    descs, rate, ch, si = entries[0]
     bs = descs["block_size"].astype(np.uint64) * descs["n_channels"].astype(np.uint64)
     out_offs = np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64) if descs.size else np.zeros(0, dtype=np.uint64)
     if descs.size and np.any(descs["n_channels"] != ch):
@@ -917,8 +1002,7 @@ def load(ctx, data, verify_md5=False):
     total = int(bs.sum())
     out = torch.zeros(total, dtype=torch.float32, device="cuda:%d" % ctx.device)
     if descs.size:
-        arena = _arena_on_device(ctx, [(0, a)], a.size)
-        res = _decode_f32(ctx, arena, a.size, descs, out_offs, out)
+        res = _decode_f32(ctx, arena, arena_len, descs, out_offs, out)
         _raise_first_failure(res)
     if verify_md5:
         n = total // max(ch, 1)
@@ -931,41 +1015,36 @@ def load(ctx, data, verify_md5=False):
     return out.view(total // max(ch, 1), ch), rate
 
 
-def _decode_streams(ctx, arrs, all_descs, starts, out_len):
-    """Whole streams `arrs` (uint8; their frames `all_descs`) decoded with one plan and one run into a zeroed float tensor of `out_len`
-    samples, stream k's interleaved samples from index starts[k] on.  The streams sit in one arena at 16-byte aligned places and every
-    frame reads no further than its own stream's end.  Returns (tensor, per-frame results or None, index of each stream's first frame)."""
+def _decode_streams(ctx, arena, arena_len, all_descs, starts, out_len):
+    """The streams of `arena` (_index_streams; their frames `all_descs`) decoded with one plan and one run into a zeroed float tensor of
+    `out_len` samples, stream k's interleaved samples from index starts[k] on.  Returns (tensor, per-frame results or None, index of
+    each stream's first frame)."""
     import torch
-    pieces, descs, offs, base = [], [], [], 0
-    for a, d, start in zip(arrs, all_descs, starts):
-        d = d.copy()
-        end = base + a.size
-        d["byte_off"] += np.uint64(base)
-        d["max_bytes"] = np.minimum(d["max_bytes"].astype(np.uint64), np.uint64(end) - d["byte_off"]).astype(np.uint32)
+    offs = []
+    for d, start in zip(all_descs, starts):
         bs = d["block_size"].astype(np.uint64) * d["n_channels"].astype(np.uint64)
         offs.append(np.uint64(start) + np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64) if d.size else np.zeros(0, np.uint64))
-        descs.append(d)
-        pieces.append((base, a))
-        base = ((end + 15) // 16) * 16
     out = torch.zeros(out_len, dtype=torch.float32, device="cuda:%d" % ctx.device)
-    first = np.cumsum([0] + [d.size for d in descs])
-    descs = np.concatenate(descs) if descs else np.zeros(0, dtype=FRAME_DESC_DTYPE)
+    first = np.cumsum([0] + [d.size for d in all_descs])
+    descs = np.concatenate(all_descs) if all_descs else np.zeros(0, dtype=FRAME_DESC_DTYPE)
     if not descs.size:
         return out, None, first
-    arena = _arena_on_device(ctx, pieces, base)
-    return out, _decode_f32(ctx, arena, base, descs, np.concatenate(offs).astype(np.uint64), out), first
+    return out, _decode_f32(ctx, arena, arena_len, descs, np.concatenate(offs).astype(np.uint64), out), first
 
 
 def load_batch(ctx, streams, verify_md5=False):
     """Several whole FLAC streams to (float32 tensor [N, T_max, C] on the context's GPU, zero-padded; lengths int64 [N]; sample rates)
-    with one plan and one run: the streams sit in one arena at 16-byte aligned places, every frame reads no further than its own
-    stream's end.  T_max is rounded up to a multiple of 8 so that every block starts on 32 bytes (the float tiers' alignment).
+    with one upload, one Context.index_streams call (one per 4 GiB of streams) and one plan and one run: the streams sit in one arena at
+    16-byte aligned places, every frame reads no further than its own stream's end.  T_max is rounded up to a multiple of 8 so that every block starts on 32 bytes (the float tiers' alignment).
     Raises ValueError when the streams differ in their channel count, ClaxonError on the first failing frame.  verify_md5: then
     checks every stream against its STREAMINFO as load(verify_md5=True) does, all MD5s in one call; ClaxonError names the first
     stream that fails."""
     import torch
     arrs = [_u8(s) for s in streams]
-    idx = [_index_stream(ctx, a) for a in arrs]
+    arena, arena_len, idx = _index_streams(ctx, arrs)
+    for e in idx:
+        if isinstance(e, ClaxonError):
+            raise e
     chans = {c for _, _, c, _ in idx}
     if len(chans) > 1:
         raise ValueError("load_batch: the streams differ in their channel count (%s)" % sorted(chans))
@@ -975,7 +1054,7 @@ def load_batch(ctx, streams, verify_md5=False):
     for k, (d, _, _, _) in enumerate(idx):
         if d.size and np.any(d["n_channels"] != ch):
             raise ClaxonError(FORMAT_ERROR, 0, "stream %d: its frames differ in their channel count" % k)
-    out, res, first = _decode_streams(ctx, arrs, [d for d, _, _, _ in idx], [k * t_max * ch for k in range(len(arrs))],
+    out, res, first = _decode_streams(ctx, arena, arena_len, [d for d, _, _, _ in idx], [k * t_max * ch for k in range(len(arrs))],
                                       len(arrs) * t_max * ch)
     if res is not None:
         bad = np.nonzero(np.asarray(res["status"]) != OK)[0]
@@ -1015,21 +1094,19 @@ def verify(ctx, streams):
     frame's status and message, a sample count other than STREAMINFO's, or "MD5 signature mismatch".
     The decoded audio of the whole call stays on the device, 4 bytes per sample, until the call returns: pass a corpus in chunks."""
     verdicts = [None] * len(streams)
-    entries, arrs, all_descs, starts, at = [], [], [], [], 0     # entries: (k, STREAMINFO, samples per channel, samples)
-    for k, s in enumerate(streams):
-        a = _u8(s)
-        try:
-            d, _, ch, si = _index_stream(ctx, a)
-        except ClaxonError as e:
+    entries, all_descs, starts, at = [], [], [], 0     # entries: (k, STREAMINFO, samples per channel, samples)
+    arena, arena_len, idx = _index_streams(ctx, [_u8(s) for s in streams])
+    for k, e in enumerate(idx):
+        if isinstance(e, ClaxonError):
             verdicts[k] = Verdict(False, False, e.status, e.message, 0)
             continue
+        d, _, ch, si = e
         total = int((d["block_size"].astype(np.int64) * d["n_channels"].astype(np.int64)).sum())
         entries.append((k, si, total // max(ch, 1), total))
-        arrs.append(a)
         all_descs.append(d)
         starts.append(at)
         at += ((total + 7) // 8) * 8
-    out, res, first = _decode_streams(ctx, arrs, all_descs, starts, max(at, 1))
+    out, res, first = _decode_streams(ctx, arena, arena_len, all_descs, starts, max(at, 1))
     todo = []
     for (k, si, n, total), at, f0, f1 in zip(entries, starts, first[:-1], first[1:]):
         bad = np.nonzero(np.asarray(res["status"][f0:f1]) != OK)[0] if f1 > f0 else []

@@ -9,6 +9,7 @@
 #include "clx_lanes.hip"
 #include "clx_lean.hip"
 #include "clx_md5.hip"
+#include "clx_index.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -243,6 +244,9 @@ struct clx_ctx {
     std::string last_error;
     clx_stream_slot slots[3];
     size_t stream_chunk = 0;          // frames per chunk of clx_decode_frames_stream (0: the default rule)
+    // scratch of clx_index_streams_device: kept until clx_destroy, regrown only by a call that needs more than any before (idx_reserve)
+    struct IdxBuf { void* p = nullptr; size_t cap = 0; };
+    IdxBuf idx_arena, idx_tab, idx_mask, idx_blk, idx_pos, idx_sid, idx_hdr, idx_crc;
 };
 
 // K2 build by batch size (groups of 64 predictor slots) unless CLX_K2_LATENCY / CLX_K2_THROUGHPUT force one
@@ -400,6 +404,8 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
         if (sl.h_res) (void)hipHostFree(sl.h_res);
         if (sl.st) (void)hipStreamDestroy(sl.st);
     }
+    for (clx_ctx::IdxBuf* b : { &ctx->idx_arena, &ctx->idx_tab, &ctx->idx_mask, &ctx->idx_blk, &ctx->idx_pos, &ctx->idx_sid, &ctx->idx_hdr, &ctx->idx_crc })
+        if (b->p) (void)hipFree(b->p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2183,6 +2189,90 @@ extern "C" int clx_index_frames_device(clx_ctx* ctx, const uint8_t* data, size_t
     if (headers) std::copy(h.begin(), h.end(), headers);
     *n_found = d.size();
     return CLX_OK;
+}
+
+// The segmented indexer (clx_index.hip): every stream of the arena in one pass.  Four launches and two waits on the stream per call
+// whatever n_streams is.  Scratch lives on the context until clx_destroy and only grows: a buffer that is too small is freed and
+// allocated anew (hipFree waits for the whole device) -- the arena copy, table, masks and counts before the call's first launch, the
+// candidate lists after meeting 1, when the stream is idle.  A call that needs no more than an earlier one allocates nothing.
+namespace {
+bool idx_reserve(clx_ctx* ctx, clx_ctx::IdxBuf& b, size_t bytes, const char* what) {
+    if (bytes <= b.cap) return true;
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    const size_t want = bytes + bytes / 4 + 256;
+    if (!hip_ok(ctx, hipMalloc(&b.p, want), what)) return false;
+    b.cap = want;
+    return true;
+}
+#define IDX_TRY(call) do { if (!hip_ok(ctx, (call), #call)) { err = ctx->last_error; return false; } } while (0)
+struct IdxDev {                                           // clx_idx_run's device side
+    clx_ctx* ctx; const uint8_t* arena; uint32_t flags; std::string& err;
+    const uint8_t* d_arena = nullptr;
+    bool reserve(clx_ctx::IdxBuf& b, size_t bytes, const char* what) {
+        if (idx_reserve(ctx, b, bytes, what)) return true;
+        err = ctx->last_error;
+        return false;
+    }
+    bool scan(const std::vector<clx_idx_stream>& tab, uint64_t chunk0, uint64_t n_chunks, uint32_t n_blocks, uint32_t* n_cand) {
+        IDX_TRY(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        d_arena = arena;
+        if (!(flags & CLX_ARENA_ON_DEVICE)) {              // one upload; the padding behind the last stream is never interpreted
+            const size_t lo = (size_t)chunk0 * 16u, hi = (size_t)(chunk0 + n_chunks) * 16u;
+            size_t end = 0;
+            for (const clx_idx_stream& s : tab) end = std::max<size_t>(end, (size_t)s.end);
+            if (!reserve(ctx->idx_arena, hi + 32u, "hipMalloc arena")) return false;
+            IDX_TRY(hipMemcpyAsync((uint8_t*)ctx->idx_arena.p + lo, arena + lo, end - lo, hipMemcpyHostToDevice, st));
+            d_arena = (const uint8_t*)ctx->idx_arena.p;
+        }
+        if (!reserve(ctx->idx_tab, tab.size() * sizeof(clx_idx_stream), "hipMalloc stream table") ||
+            !reserve(ctx->idx_mask, (size_t)n_chunks * 2u, "hipMalloc masks") ||
+            !reserve(ctx->idx_blk, ((size_t)n_blocks * 2u + 1u) * 4u, "hipMalloc counts")) return false;
+        uint32_t* d_count = (uint32_t*)ctx->idx_blk.p; uint32_t* d_base = d_count + n_blocks;
+        IDX_TRY(hipMemcpyAsync(ctx->idx_tab.p, tab.data(), tab.size() * sizeof(clx_idx_stream), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(clx_k_idx_scan, dim3(n_blocks), dim3(256), 0, st, d_arena, (const clx_idx_stream*)ctx->idx_tab.p, (uint32_t)tab.size(),
+                           chunk0, n_chunks, (uint16_t*)ctx->idx_mask.p, d_count);
+        hipLaunchKernelGGL(clx_k_idx_offsets, dim3(1), dim3(256), 0, st, (const uint32_t*)d_count, n_blocks, d_base);
+        IDX_TRY(hipGetLastError());
+        IDX_TRY(hipMemcpyAsync(n_cand, d_base + n_blocks, 4, hipMemcpyDeviceToHost, st));
+        IDX_TRY(hipStreamSynchronize(st));                                                           // meeting 1: how many candidates
+        return true;
+    }
+    bool lists(const std::vector<clx_idx_stream>& tab, uint64_t chunk0, uint64_t n_chunks, uint32_t n_blocks, uint32_t n_cand,
+               uint64_t* pos, uint32_t* sid, uint8_t* hdr, uint16_t* crc) {
+        hipStream_t st = ctx->stream;
+        if (!reserve(ctx->idx_pos, (size_t)n_cand * 8u, "hipMalloc candidates") || !reserve(ctx->idx_sid, (size_t)n_cand * 4u, "hipMalloc candidates") ||
+            !reserve(ctx->idx_hdr, (size_t)n_cand * CLX_IDX_HDR_BYTES, "hipMalloc candidates") ||
+            !reserve(ctx->idx_crc, (size_t)n_cand * 2u, "hipMalloc candidates")) return false;
+        const clx_idx_stream* d_tab = (const clx_idx_stream*)ctx->idx_tab.p;
+        hipLaunchKernelGGL(clx_k_idx_compact, dim3(n_blocks), dim3(256), 0, st, d_arena, d_tab, (uint32_t)tab.size(), chunk0, n_chunks,
+                           (const uint16_t*)ctx->idx_mask.p, (const uint32_t*)ctx->idx_blk.p + n_blocks, n_cand, (uint64_t*)ctx->idx_pos.p,
+                           (uint32_t*)ctx->idx_sid.p, (uint8_t*)ctx->idx_hdr.p);
+        hipLaunchKernelGGL(clx_k_idx_span_crc, dim3(n_cand), dim3(64), 0, st, d_arena, d_tab, (const uint64_t*)ctx->idx_pos.p,
+                           (const uint32_t*)ctx->idx_sid.p, n_cand, (uint16_t*)ctx->idx_crc.p);
+        IDX_TRY(hipGetLastError());
+        IDX_TRY(hipMemcpyAsync(pos, ctx->idx_pos.p, (size_t)n_cand * 8u, hipMemcpyDeviceToHost, st));
+        IDX_TRY(hipMemcpyAsync(sid, ctx->idx_sid.p, (size_t)n_cand * 4u, hipMemcpyDeviceToHost, st));
+        IDX_TRY(hipMemcpyAsync(hdr, ctx->idx_hdr.p, (size_t)n_cand * CLX_IDX_HDR_BYTES, hipMemcpyDeviceToHost, st));
+        IDX_TRY(hipMemcpyAsync(crc, ctx->idx_crc.p, (size_t)n_cand * 2u, hipMemcpyDeviceToHost, st));
+        IDX_TRY(hipStreamSynchronize(st));                                                           // meeting 2: the candidate lists
+        return true;
+    }
+};
+#undef IDX_TRY
+}  // namespace
+
+extern "C" int clx_index_streams_device(clx_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                                        const uint64_t* offs, const uint64_t* lens, const uint64_t* starts, size_t n_streams,
+                                        clx_frame_desc* descs, clx_frame_header* headers, size_t cap,
+                                        uint64_t* first_frame, uint64_t* stop_offs, size_t* n_found, uint32_t flags) {
+    if (!ctx) return CLX_API_ERROR;
+    std::string err;
+    IdxDev dev{ ctx, arena, flags, err };
+    const int st = clx_idx_run(dev, err, arena, arena_len, offs, lens, starts, n_streams, descs, headers, cap, first_frame, stop_offs, n_found,
+                               clx_parse_frame_header);
+    if (st != CLX_OK) ctx->last_error = err;
+    return st;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -488,6 +488,31 @@ int clx_index_frames_device(clx_ctx* ctx, const uint8_t* data, size_t len, size_
                             clx_frame_desc* descs, clx_frame_header* headers, size_t cap,
                             size_t* n_found, size_t* stop_off, uint32_t flags);
 
+/* The device indexer for a whole shard: `n_streams` streams that lie in one arena, indexed in one pass (a fixed number of
+ * kernel launches, allocations and host-device synchronisations per call, whatever n_streams is).  Stream k is
+ * arena[offs[k] .. offs[k] + lens[k]); its indexing begins at offs[k] + starts[k] (what clx_read_stream_header reported
+ * as the audio offset, 0 for a bare frame sequence; starts == NULL: all zero).  offs[k] is a multiple of 16 and the
+ * streams ascend without overlap.
+ * Contract: for every k the frames, headers and stop offset are exactly what
+ *   clx_index_frames(arena + offs[k], lens[k], starts[k], ...)
+ * returns for that stream alone, with byte_off and stop_offs[k] rebased onto the arena (offs[k] added); max_bytes still
+ * ends at the stream's own end.  Nothing outside [offs[k] + starts[k], offs[k] + lens[k]) influences stream k's answer,
+ * and no stream's content makes the call fail (candidates are held as one bit per byte position: nothing overflows).
+ * Frames of stream k are descs[first_frame[k] .. first_frame[k + 1]) (first_frame has n_streams + 1 entries);
+ * *n_found = first_frame[n_streams].  If the frames do not fit `cap` the call returns CLX_API_ERROR with *n_found set
+ * to the number needed (first_frame and stop_offs are complete, descs / headers untouched): call again with that cap.
+ * CLX_API_ERROR with a clx_last_error that names the stream for a misaligned, overlapping or out-of-arena stream and for
+ * starts[k] > lens[k]; also for NULL outputs (headers may be NULL) and an arena of 4 GiB or more.
+ * `arena` is a host pointer (uploaded once), or with CLX_ARENA_ON_DEVICE a device pointer under the rule of
+ * clx_index_frames_device.
+ * Memory: the call's device scratch (2 bytes per 16 arena bytes, 34 bytes per candidate header, and for a host arena
+ * its device copy) belongs to the context and is kept until clx_destroy; a call that needs more than any call before
+ * frees and reallocates it (which waits for the device), later calls of that size allocate nothing. */
+int clx_index_streams_device(clx_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                             const uint64_t* offs, const uint64_t* lens, const uint64_t* starts, size_t n_streams,
+                             clx_frame_desc* descs, clx_frame_header* headers, size_t cap,
+                             uint64_t* first_frame, uint64_t* stop_offs, size_t* n_found, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif
