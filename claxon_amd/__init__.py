@@ -30,6 +30,7 @@ POOL = 16384                # pipelined submissions: the scan and the 16-bit tie
 OUT_PCM24 = 32768           # the same with packed 24-bit samples (3 bytes each), written by the general lane kernels
 OUT_F32 = 65536             # the same with channel-interleaved float32 normalized to [-1, 1): (float)v * 2^-(bps-1), 4 bytes per sample
 SAMPLE_F32 = 0x104          # sample format of interleave / decode_frames_stream: the floats of OUT_F32 (next to sample_bytes 1..4)
+WINDOW_TC, WINDOW_CT = 0, 1   # clx_gather_windows layouts: [B, L, C] and [B, C, L]
 SUBMIT_DEPTH = 24           # CLX_SUBMIT_DEPTH: the most submissions a Batch keeps in flight (Batch.submit_depth: this batch's)
 
 
@@ -96,13 +97,13 @@ EXPORTS = [
     "clx_batch_kernel_ms", "clx_batch_kernel_name", "clx_batch_destroy", "clx_read_stream_header", "clx_read_stream_header_ext",
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
-    "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device",
+    "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -175,6 +176,7 @@ def lib():
     L.clx_index_streams_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, C.POINTER(sz), C.c_uint32]
     L.clx_interleave.argtypes = [vp, vp, vp, sz, vp, vp, vp, C.c_uint32, C.c_uint32]
     L.clx_md5_streams.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, sz, vp, vp]
+    L.clx_gather_windows.argtypes = [vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -634,6 +636,24 @@ class Context:
                                           _np_ptr(out), None))
         return out
 
+    def gather_windows(self, src, src_first, valid, window_len, channels, layout, out, stream=None):
+        """clx_gather_windows: window k = valid[k] samples per channel from float src_first[k] of `src` on (channel-interleaved float32,
+        what OUT_F32 writes), zero-filled to window_len, written to `out` as [B, L, C] (WINDOW_TC) or [B, C, L] (WINDOW_CT).  `src` and
+        `out` are CUDA float32 tensors or device pointers.  Asynchronous on `stream` (a torch stream or a raw handle; None: the current
+        torch stream when `out` is a tensor, else the context's own): nothing is waited for, before or after."""
+        src_first = np.ascontiguousarray(src_first, dtype=np.uint64).reshape(-1)
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if src_first.size != valid.size:
+            raise ValueError("gather_windows: src_first and valid differ in length")
+        if stream is None and hasattr(out, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(out.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        ptr = [t.data_ptr() if hasattr(t, "data_ptr") else (int(t) if t else None) for t in (src, out)]
+        self._check(lib().clx_gather_windows(self._h, ptr[0], _np_ptr(src_first), _np_ptr(valid), src_first.size, int(window_len), int(channels),
+                                             int(layout), ptr[1], C.c_void_p(handle) if handle else None))
+        return out
+
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
         a = _u8(arena)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -896,13 +916,14 @@ def _index_arena(ctx, arena, offs, lens, starts, limit=INDEX_CALL_BYTES):
     return np.concatenate(descs), np.array(first, dtype=np.uint64), np.array(stops, dtype=np.uint64)
 
 
-def _index_streams(ctx, arrs):
+def _index_streams(ctx, arrs, short=None):
     """Whole FLAC streams `arrs` (uint8) made ready to decode: their headers parsed on the host, the streams whose header parses laid
     out in one arena at 16-byte aligned places, that arena uploaded once and indexed with one Context.index_streams call.  Returns
     (arena tensor | None, arena length, entries): entries[k] is (descs, sample_rate, channels, STREAMINFO) -- the descriptors address
     the arena and read no further than the stream's own end -- or the ClaxonError that stream raises.  Bytes the indexer cannot chain
     up (a damaged or truncated frame) become one more descriptor when they start with a valid frame header, so that decoding reports
-    that frame's error as the reference's reader would; a header that does not parse there is the stream's error."""
+    that frame's error as the reference's reader would; a header that does not parse there is the stream's error.  `short`: a list that
+    gets, for every stream with an entry of descriptors, (k, byte of the stream where its index stopped) when that is not its end."""
     entries, live, offs, starts, infos, base = [None] * len(arrs), [], [], [], [], 0
     for k, a in enumerate(arrs):
         st, msg, si, off = read_stream_header(a)
@@ -919,6 +940,8 @@ def _index_streams(ctx, arrs):
         a, si = arrs[k], infos[j]
         d, stop, end = descs[int(first[j]):int(first[j + 1])], int(stops[j]), offs[j] + a.size
         if stop < end:
+            if short is not None:
+                short.append((k, stop - offs[j]))
             st, msg, h = parse_frame_header(a[stop - offs[j]:], True)
             if st != OK:
                 entries[k] = ClaxonError(st, msg)
@@ -1130,3 +1153,129 @@ def verify(ctx, streams):
             why, _ = _stream_problem(si, n, dg)
             verdicts[k] = Verdict(why is None, True, OK if why is None else FORMAT_ERROR, why or "", n)
     return verdicts
+
+
+# ---- sample windows from resident streams -----------------------------------------------------------------------------------------
+
+_LAYOUTS = {"tc": WINDOW_TC, "ct": WINDOW_CT}
+
+
+class StreamSet:
+    """FLAC streams resident on the GPU, uploaded and indexed once (open_streams), from which read() draws batches of fixed-length
+    sample windows by decoding only the frames that cover them.  Per stream: lengths (int64 tensor, samples per channel: the sum of
+    the indexed block sizes, load()'s T), channels, sample_rates, bits_per_sample, and problems -- None, or the ClaxonError that keeps
+    the stream from being read (0 / None in the other lists).  frames_decoded counts the frames read() has handed to the decoder."""
+
+    def __init__(self, ctx, streams):
+        import torch
+        self.ctx = ctx
+        arrs = [_u8(s) for s in streams]
+        n, short = len(arrs), []
+        self._arena, self._arena_len, entries = _index_streams(ctx, arrs, short)
+        short = dict(short)
+        self.problems, self.channels, self.sample_rates, self.bits_per_sample = [None] * n, [0] * n, [0] * n, [0] * n
+        lengths = np.zeros(n, dtype=np.int64)
+        self._first = np.zeros(n + 1, dtype=np.int64)         # stream k's frames are rows _first[k] .. _first[k + 1] of the tables below
+        self._base = np.zeros(n + 1, dtype=np.int64)          # ... and its samples sit at _base[k] .. in the set's one sample axis
+        descs = []
+        for k, e in enumerate(entries):
+            if isinstance(e, ClaxonError):
+                self.problems[k] = e
+            elif k in short:
+                self.problems[k] = ClaxonError(FORMAT_ERROR, 0, "the frame index stops at byte %d of %d" % (short[k], arrs[k].size))
+            elif e[0].size and np.any(e[0]["n_channels"] != e[2]):
+                self.problems[k] = ClaxonError(FORMAT_ERROR, 0, "the stream's frames differ in their channel count")
+            else:
+                d, self.sample_rates[k], self.channels[k], si = e
+                self.bits_per_sample[k] = int(d["bps"][0]) if d.size else int(si.bits_per_sample)
+                lengths[k] = int(d["block_size"].astype(np.int64).sum())
+                descs.append(d)
+            self._first[k + 1] = self._first[k] + (descs[-1].size if self.problems[k] is None else 0)
+            self._base[k + 1] = self._base[k] + lengths[k]
+        self._descs = np.concatenate(descs) if descs else np.zeros(0, dtype=FRAME_DESC_DTYPE)
+        bs = self._descs["block_size"].astype(np.int64)
+        self._start = np.cumsum(bs) - bs                      # a frame's first sample in the set's sample axis (load()'s count: by block size)
+        self._local = self._start - np.repeat(self._base[:-1], np.diff(self._first))      # ... and within its own stream
+        self._lengths = lengths
+        self.lengths = torch.from_numpy(lengths.copy())
+        self.frames_decoded = 0
+
+    def __len__(self):
+        return len(self.problems)
+
+    def close(self):
+        """Drops the arena (the device memory goes back to torch's allocator); the set reads nothing afterwards."""
+        self._arena = None
+        self._descs = None
+
+    def read(self, stream_ids, starts, length, layout="tc"):
+        """A batch of windows: window k is samples [starts[k], starts[k] + length) of stream stream_ids[k], positions counted as load()
+        counts them (by cumulative block size in frame order; the frame headers' sample numbers are not consulted).  Returns (float32
+        tensor on the context's GPU, contiguous: [B, length, C] for layout "tc", [B, C, length] for "ct"; valid): valid[k] =
+        clamp(lengths[s] - starts[k], 0, length) as an int64 tensor, the rest of a window is zeros, and a window that starts at or
+        behind its stream's end is all zeros and decodes nothing.  Only the frames that cover a window are decoded, with one plan
+        (OUT_F32 | VERIFY_CRC16) and one run for the call, into a scratch tensor where each window's frames sit back to back from a
+        multiple of 8 floats; one clx_gather_windows launch then cuts the windows out of it.  Frames shared by overlapping windows are
+        decoded once per window.  Raises ValueError for a negative start or length, an unknown stream id or layout, or windows whose
+        streams differ in channel count; the stream's `problems` entry when a window names a problem stream; ClaxonError with a
+        failing frame's status and message, " (window k, stream s)" appended.  The result is ready on the current torch stream."""
+        import torch
+        if self._descs is None:
+            raise ValueError("read: the stream set is closed")
+        if layout not in _LAYOUTS:
+            raise ValueError("read: layout must be 'tc' or 'ct', not %r" % (layout,))
+        length = int(length)
+        if length < 0:
+            raise ValueError("read: length must not be negative")
+        sid = np.asarray(stream_ids, dtype=np.int64).reshape(-1)
+        st = np.asarray(starts, dtype=np.int64).reshape(-1)
+        if sid.size != st.size:
+            raise ValueError("read: stream_ids and starts differ in length")
+        if sid.size and (sid.min() < 0 or sid.max() >= len(self)):
+            raise ValueError("read: unknown stream id")
+        if st.size and st.min() < 0:
+            raise ValueError("read: a window starts before its stream")
+        for s in sid.tolist():
+            if self.problems[s] is not None:
+                raise self.problems[s]
+        chans = {self.channels[s] for s in set(sid.tolist())} or {c for c, p in zip(self.channels, self.problems) if p is None}
+        if len(chans) > 1 and sid.size:
+            raise ValueError("read: the windows' streams differ in their channel count (%s)" % sorted(chans))
+        ch = chans.pop() if len(chans) == 1 else 0
+        B, dev = sid.size, "cuda:%d" % self.ctx.device
+        valid = np.clip(self._lengths[sid] - st, 0, length)
+        shape = (B, length, ch) if layout == "tc" else (B, ch, length)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        if B == 0 or length == 0:
+            return out, torch.from_numpy(valid)
+        live = np.nonzero(valid > 0)[0]
+        # the covering frames: a searchsorted on the cumulative sample starts (one axis for the whole set: a live window lies inside its stream)
+        f0 = np.searchsorted(self._start, self._base[sid[live]] + st[live], side="right") - 1
+        f1 = np.searchsorted(self._start, self._base[sid[live]] + st[live] + valid[live] - 1, side="right") - 1
+        cnt = f1 - f0 + 1
+        ends = np.cumsum(cnt)
+        rows = np.repeat(f0 - (ends - cnt), cnt) + np.arange(int(ends[-1]) if live.size else 0)
+        span = (self._start[f1] + self._descs["block_size"][f1].astype(np.int64) - self._start[f0]) * ch      # floats of a window's frames
+        room = (span + 7) // 8 * 8
+        base = np.cumsum(room) - room
+        out_offs = np.repeat(base - self._start[f0] * ch, cnt) + self._start[rows] * ch
+        src_first = np.zeros(B, dtype=np.uint64)
+        src_first[live] = base + (st[live] - self._local[f0]) * ch
+        scratch = torch.empty(max(int(room.sum()), 8), dtype=torch.float32, device=dev)
+        if rows.size:
+            res = _decode_f32(self.ctx, self._arena, self._arena_len, self._descs[rows], out_offs.astype(np.uint64), scratch)
+            self.frames_decoded += int(rows.size)
+            bad = np.nonzero(np.asarray(res["status"]) != OK)[0]
+            if bad.size:
+                k = int(live[int(np.searchsorted(ends, int(bad[0]), side="right"))])
+                _raise_first_failure(res, " (window %d, stream %d)" % (k, int(sid[k])))
+        self.ctx.gather_windows(scratch, src_first, valid, length, ch, _LAYOUTS[layout], out)
+        return out, torch.from_numpy(valid)
+
+
+def open_streams(ctx, streams):
+    """Whole FLAC streams (bytes-like) made resident for StreamSet.read: one arena, uploaded once and indexed with one
+    Context.index_streams pass; the arena and the per-stream frame index stay alive in the returned StreamSet.  Like verify() it never
+    raises for a bad stream: StreamSet.problems[k] holds the ClaxonError of a stream with a header error, an index that stops short of
+    the stream's end, frames that differ in channel count or a frame header without bits per sample."""
+    return StreamSet(ctx, streams)

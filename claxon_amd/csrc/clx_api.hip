@@ -10,6 +10,7 @@
 #include "clx_lean.hip"
 #include "clx_md5.hip"
 #include "clx_index.hip"
+#include "clx_window.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -247,6 +248,13 @@ struct clx_ctx {
     // scratch of clx_index_streams_device: kept until clx_destroy, regrown only by a call that needs more than any before (idx_reserve)
     struct IdxBuf { void* p = nullptr; size_t cap = 0; };
     IdxBuf idx_arena, idx_tab, idx_mask, idx_blk, idx_pos, idx_sid, idx_hdr, idx_crc;
+    // scratch of clx_gather_windows: the window table on the device and its pinned staging.  A table that has to grow is replaced
+    // before the call queues anything; the one it replaces may still be read by an earlier call's launch, so it is kept (win_old)
+    // until clx_destroy.  ev_win_up: behind the last table upload (the staging is rewritten only after it); ev_win_done: behind the
+    // last launch (the device table is rewritten only after it, whichever stream that launch went to).
+    clx_win_job* d_win = nullptr; clx_win_job* h_win = nullptr; size_t win_cap = 0;
+    std::vector<void*> win_old_dev, win_old_host;
+    hipEvent_t ev_win_up = nullptr, ev_win_done = nullptr; bool win_used = false;
 };
 
 // K2 build by batch size (groups of 64 predictor slots) unless CLX_K2_LATENCY / CLX_K2_THROUGHPUT force one
@@ -406,6 +414,12 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     }
     for (clx_ctx::IdxBuf* b : { &ctx->idx_arena, &ctx->idx_tab, &ctx->idx_mask, &ctx->idx_blk, &ctx->idx_pos, &ctx->idx_sid, &ctx->idx_hdr, &ctx->idx_crc })
         if (b->p) (void)hipFree(b->p);
+    if (ctx->win_used) (void)hipEventSynchronize(ctx->ev_win_done);
+    if (ctx->ev_win_up) (void)hipEventDestroy(ctx->ev_win_up);
+    if (ctx->ev_win_done) (void)hipEventDestroy(ctx->ev_win_done);
+    ctx->win_old_dev.push_back(ctx->d_win); ctx->win_old_host.push_back(ctx->h_win);
+    for (void* p : ctx->win_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->win_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1398,6 +1412,39 @@ extern "C" int clx_md5_streams(clx_ctx* ctx, const void* d_samples, uint32_t sam
     if (d_jobs) (void)hipFree(d_jobs);
     if (d_dig) (void)hipFree(d_dig);
     return ok ? CLX_OK : CLX_API_ERROR;
+}
+
+extern "C" int clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const uint32_t* valid, size_t n_windows,
+                                  uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    uint32_t n_tiles = 0;
+    const char* why = clx_window_check(d_src, src_first, valid, n_windows, window_len, channels, layout, d_out, &n_tiles);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_win_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_win_up, hipEventDisableTiming));
+    if (!ctx->ev_win_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_win_done, hipEventDisableTiming));
+    if (n_windows > ctx->win_cap) {                            // a larger table, before anything is queued; the old one is not freed here
+        const size_t want = n_windows + n_windows / 2 + 64;
+        clx_win_job* d = nullptr; clx_win_job* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(clx_win_job)), "hipMalloc window table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(clx_win_job), hipHostMallocDefault), "hipHostMalloc window table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_win) { ctx->win_old_dev.push_back(ctx->d_win); ctx->win_old_host.push_back(ctx->h_win); }
+        ctx->d_win = d; ctx->h_win = h; ctx->win_cap = want;
+    } else if (ctx->win_used) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_win_up));     // (the upload only: the earlier launch itself is not waited for)
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_win_done, 0));
+    }
+    clx_window_fill(ctx->h_win, src_first, valid, n_windows);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_win, ctx->h_win, n_windows * sizeof(clx_win_job), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_win_up, stream));
+    ctx->win_used = true;                                      // (from here on the staging and the table are in use)
+    hipLaunchKernelGGL(clx_k_window, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_win::kThreads), 0, stream, (const uint32_t*)d_src,
+                       (const clx_win_job*)ctx->d_win, n_tiles, window_len, channels, layout, (uint32_t*)d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_win_done, stream));
+    return CLX_OK;
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

@@ -368,6 +368,23 @@ int  clx_batch_interleave(clx_batch* b, const int32_t* d_planar, void* d_pcm, ui
  * One stream hashes at a single lane's rate: the device wins by the number of streams (README: measured rates). */
 int  clx_md5_streams(clx_ctx* ctx, const void* d_samples, uint32_t sample_format, const uint64_t* first_sample,
                      const uint64_t* n_samples, const uint8_t* bps, size_t n_streams, uint8_t* digests, void* stream);
+/* A dense batch of fixed-length sample windows gathered from decoded audio on the device, in one launch (clx_k_window).  d_src is a
+ * device buffer of channel-interleaved float32, what CLX_OUT_F32 writes, `channels` (1..8) floats per sample.  Window k is the
+ * valid[k] <= window_len samples per channel from float index src_first[k] on (the window's first sample, channel 0; no alignment
+ * beyond 4 bytes).  d_out (device, n_windows * window_len * channels floats) gets
+ *   CLX_WINDOW_TC: out[k][t][c] = d_src[src_first[k] + t*channels + c]        a [B, L, C] tensor
+ *   CLX_WINDOW_CT: out[k][c][t] = the same value                              a [B, C, L] tensor (channels first)
+ * and 0.0f for every t >= valid[k]: the call writes all of d_out, which need not be cleared.  No float of d_src outside
+ * [src_first[k], src_first[k] + valid[k]*channels) is read.  All offsets are 64-bit.  src_first and valid are host arrays, copied
+ * before the call returns into scratch that the context owns (grown, when it must, before anything is queued; released by
+ * clx_destroy).  Asynchronous: queued on `stream` (NULL: the context's) after what is already there, e.g. the clx_batch_run that
+ * decodes d_src; d_src and d_out stay valid until that stream has passed the call.  CLX_API_ERROR (clx_last_error says why) for
+ * channels outside 1..8, an unknown layout, a valid[k] above window_len, or a null pointer while n_windows * window_len > 0;
+ * n_windows == 0 or window_len == 0 succeeds and launches nothing. */
+enum { CLX_WINDOW_TC = 0, CLX_WINDOW_CT = 1 };
+int  clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const uint32_t* valid,
+                        size_t n_windows, uint32_t window_len, uint32_t channels, uint32_t layout,
+                        void* d_out, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
