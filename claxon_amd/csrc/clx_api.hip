@@ -1676,6 +1676,9 @@ extern "C" int clx_decode_frames_stream(clx_ctx* ctx, const uint8_t* arena, size
         for (size_t i = lo + 1; i < hi && !gaps; ++i)
             gaps = out_sample_offsets[i] != out_sample_offsets[i - 1] + (uint64_t)frames[i - 1].n_channels * frames[i - 1].block_size;
         const bool clear_out = out != nullptr && (sample_bytes != 0u || gaps);
+        // (the gap between this chunk's last block and the next chunk's first is in nobody's slice: cleared here, on the host)
+        if (out != nullptr && hi < n && out_sample_offsets[hi] > o1)
+            std::memset((uint8_t*)out + o1 * (sbytes ? sbytes : 4u), 0, (size_t)(out_sample_offsets[hi] - o1) * (sbytes ? sbytes : 4u));
         const bool ok =
             hip_ok(ctx, hipMemsetAsync(S.d_arena + (arena_alloc - 48), 0, 48, S.st), "memset") &&
             hip_ok(ctx, hipMemcpyAsync(S.d_arena, arena + a0, span, hipMemcpyHostToDevice, S.st), "H2D arena") &&

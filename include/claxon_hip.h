@@ -276,7 +276,10 @@ int clx_decode_frames_multi(clx_ctx* const* ctxs, size_t n_ctx, const uint8_t* a
  *                      at byte out_sample_offsets[i] * sample_bytes -- what callers of the reference write out
  *                      (examples/decode.rs:48-62), half the bytes over the link for 16-bit audio
  *   out == NULL      : nothing is copied back but the results (decode throughput with the upload included)
- * Samples of failed frames read as zeros.  Frames in increasing, non-overlapping output order.  Buffers from clx_host_alloc
+ * Frames in increasing, non-overlapping output order; they may leave gaps.  `out` is written whole from the first frame's block to
+ * the end of the last one's: samples of failed frames read as zeros, and so does every gap between two blocks (the chunks come back
+ * as whole slices; a gap that falls between two chunks is cleared on the host, by the calling thread, so very large gaps cost host
+ * time).  Nothing in front of the first block or behind the last one is written.  Buffers from clx_host_alloc
  * (pinned) make the copies asynchronous at link speed; any host memory works. */
 int   clx_decode_frames_stream(clx_ctx* ctx, const uint8_t* arena, size_t arena_len, const clx_frame_desc* frames, size_t n,
                                void* out, uint32_t sample_bytes, const uint64_t* out_sample_offsets,
@@ -307,6 +310,22 @@ int clx_decode_subframes(clx_ctx* ctx, const uint8_t* arena, size_t arena_len,
  * (NULL = the context's own stream). */
 int  clx_batch_create(clx_ctx* ctx, const clx_frame_desc* frames, size_t n,
                       const uint64_t* out_sample_offsets, uint32_t flags, clx_batch** out);
+/* Where a planned batch writes (clx_batch_run, clx_batch_submit; every kernel path and every CLX_OUT_* mode; tests/placement_cases.py
+ * holds the kernels to it, element by element):
+ *   - Frame i's block is the n_channels * block_size elements (CLX_OUT_PCM24: three bytes each) from out_sample_offsets[i] on.  The
+ *     blocks may lie anywhere in `d_out`, in any order, with gaps of any length between them and more than 4 GiB apart; they must not
+ *     overlap.  All offsets are 64-bit.
+ *   - `d_out` needs the alignment of its element type and no more: 4 bytes for planar int32_t and CLX_OUT_F32, 2 for CLX_OUT_PCM16,
+ *     none for CLX_OUT_PCM24.
+ *   - Nothing outside the blocks is written: not the bytes in front of the first block or behind the last, not a gap, not the tail of
+ *     a 16-byte or 128-byte line a block ends in.  The buffer needs no slack behind its last block.  (Inside the block of a frame that
+ *     FAILS the content is unspecified.)
+ *   - Placement costs speed, never correctness.  The fast tiers take a wave of 64 subframes when every row of it starts on 16 ADDRESS
+ *     bytes (CLX_OUT_F32: on 32) and lies within 4 GiB of the wave's lowest row; everything else goes through the general kernels,
+ *     which store a row that is off 16 bytes sample by sample.  With `d_out` itself on 32 bytes (any device allocation) that means:
+ *     planar, every out_sample_offsets[i] a multiple of 4 and block sizes a multiple of 16; CLX_OUT_PCM16 and CLX_OUT_F32, offsets a
+ *     multiple of 8; CLX_OUT_PCM24, a multiple of 16.  The wave path's vector row stores want rows on 16 address bytes too (offsets
+ *     and block sizes a multiple of 4); its kernels test the address, so a `d_out` that is off 16 bytes only takes the slower stores. */
 int  clx_batch_run(clx_batch* b, const uint8_t* d_arena, size_t arena_len,
                    int32_t* d_out, void* stream);
 /* Pipelined submission: the same work and the same results as clx_batch_run, with several submissions in flight (the reference

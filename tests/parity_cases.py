@@ -1050,6 +1050,26 @@ def escape_workload():
     return w
 
 
+OUT_BITS = {"planar": np.uint32, "pcm16": np.uint16, "pcm24": np.uint8, "f32": np.uint32}      # an element of each output mode, as bits
+
+
+def block_in_mode(v, c, bs, bps, out):
+    """A frame's planar i32 samples `v` (c channels of bs samples, `bps` bits) as its block of an output mode: "planar" (int32, as
+    they are), "pcm16" (int16, channel-interleaved low halves), "pcm24" (uint8, three little-endian bytes per interleaved sample),
+    "f32" (float32, the interleaved samples through claxon_hip.h's CLX_OUT_F32 formula)."""
+    v = np.asarray(v, dtype=np.int32)
+    if out == "planar":
+        return v
+    inter = v.reshape(c, bs).T.reshape(-1)
+    if out == "pcm16":
+        return inter.astype(np.int16)
+    if out == "pcm24":
+        u = inter.astype(np.int32).view(np.uint32)
+        return np.stack([u & 0xff, (u >> 8) & 0xff, (u >> 16) & 0xff], axis=1).astype(np.uint8).reshape(-1)
+    from f32_cases import to_f32       # (imported here: f32_cases itself imports this module)
+    return to_f32(inter, bps)
+
+
 def check_against_oracle(oracle, backend, w, arena=None, out="planar", verify_crc=True):
     """Any workload, intact or not, against the oracle: status and message of every frame; end bit and samples of every OK frame --
     planar i32, or the interleaved bytes of `out` = "pcm16" / "pcm24" / "f32" (backend.path must carry the matching CLX_OUT_* flag).
@@ -1067,18 +1087,9 @@ def check_against_oracle(oracle, backend, w, arena=None, out="planar", verify_cr
     got = np.asarray(got)
     for i in np.nonzero(st == cx.OK)[0]:
         a, c, bs = int(w.out_offs[i]), int(w.channels[i]), int(w.block_sizes[i])
-        v = ref[a:a + c * bs]
-        inter = v.reshape(c, bs).T.reshape(-1)
-        if out == "planar":
-            ok = np.array_equal(got[a:a + c * bs], v)
-        elif out == "pcm16":
-            ok = np.array_equal(got.view(np.int16)[a:a + c * bs], inter.astype(np.int16))
-        elif out == "pcm24":
-            u = inter.astype(np.int32).view(np.uint32)
-            ok = np.array_equal(got.view(np.uint8)[3 * a:3 * (a + c * bs)], np.stack([u & 0xff, (u >> 8) & 0xff, (u >> 16) & 0xff], axis=1).astype(np.uint8).reshape(-1))
-        else:
-            want = inter.astype(np.float32) * np.float32(2.0 ** (1 - int(w.bps[i])))
-            ok = np.array_equal(got.view(np.float32)[a:a + c * bs].view(np.uint32), want.view(np.uint32))
+        want = block_in_mode(ref[a:a + c * bs], c, bs, w.bps[i], out)
+        k = 3 if out == "pcm24" else 1
+        ok = np.array_equal(got.view(want.dtype)[k * a:k * (a + c * bs)].view(OUT_BITS[out]), want.view(OUT_BITS[out]))
         assert ok, "frame %d (%d ch, bs %d, %d bits, %s)" % (int(i), c, bs, int(w.bps[i]), out)
     return st, ms
 
