@@ -9,6 +9,7 @@ There is no CPU decode path: creating a :class:`Context` raises when the
 library or a gfx950 device is missing.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -98,12 +99,13 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
+    "clx_resample_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -177,6 +179,7 @@ def lib():
     L.clx_interleave.argtypes = [vp, vp, vp, sz, vp, vp, vp, C.c_uint32, C.c_uint32]
     L.clx_md5_streams.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, sz, vp, vp]
     L.clx_gather_windows.argtypes = [vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    L.clx_resample_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -652,6 +655,28 @@ class Context:
         ptr = [t.data_ptr() if hasattr(t, "data_ptr") else (int(t) if t else None) for t in (src, out)]
         self._check(lib().clx_gather_windows(self._h, ptr[0], _np_ptr(src_first), _np_ptr(valid), src_first.size, int(window_len), int(channels),
                                              int(layout), ptr[1], C.c_void_p(handle) if handle else None))
+        return out
+
+    def resample_windows(self, src, src_first, src_t0, src_n, out_t0, valid, src_rate, out_rate, window_len, channels, layout, out, stream=None):
+        """clx_resample_windows: window k = outputs out_t0[k] .. out_t0[k] + valid[k] - 1 of its stream resampled from src_rate[k] to
+        out_rate (the fixed windowed-sinc resampler of claxon_hip.h; a plain copy where the two are equal), zero-filled to window_len,
+        written to `out` as [B, L, C] (WINDOW_TC) or [B, C, L] (WINDOW_CT).  The window's source span is src_n[k] samples per channel
+        of `src` (channel-interleaved float32) from float src_first[k] on, the first of them stream sample src_t0[k]; samples outside
+        it count as zero.  `src`, `out` and `stream` as for gather_windows."""
+        arrs = [np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in ((src_first, np.uint64), (src_t0, np.int64), (src_n, np.uint32),
+                                                                           (out_t0, np.uint64), (valid, np.uint32), (src_rate, np.uint32))]
+        if len({a.size for a in arrs}) != 1:
+            raise ValueError("resample_windows: the per-window arrays differ in length")
+        for name, v in (("out_rate", out_rate), ("window_len", window_len), ("channels", channels), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("resample_windows: %s is out of range" % name)
+        if stream is None and hasattr(out, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(out.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        ptr = [t.data_ptr() if hasattr(t, "data_ptr") else (int(t) if t else None) for t in (src, out)]
+        self._check(lib().clx_resample_windows(self._h, ptr[0], *[_np_ptr(a) for a in arrs], arrs[0].size, int(out_rate), int(window_len),
+                                               int(channels), int(layout), ptr[1], C.c_void_p(handle) if handle else None))
         return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -1158,6 +1183,16 @@ def verify(ctx, streams):
 # ---- sample windows from resident streams -----------------------------------------------------------------------------------------
 
 _LAYOUTS = {"tc": WINDOW_TC, "ct": WINDOW_CT}
+RESAMPLE_RATE_LIMIT = 1 << 20          # rates are 1 .. 2^20 - 1: the width of STREAMINFO's field
+RESAMPLE_TABLE_LIMIT = 1 << 18         # the most entries of a rate pair's [n, 2W] coefficient table
+
+
+def resample_pair(src_rate, out_rate):
+    """(o, n, W) of the fixed resampler (claxon_hip.h, clx_resample_windows) for src_rate -> out_rate: the reduced pair and the
+    filter's half width in source samples; W = 0 for equal rates, where a window is a plain copy."""
+    g = math.gcd(int(src_rate), int(out_rate))
+    o, n = int(src_rate) // g, int(out_rate) // g
+    return (o, n, 0) if o == n else (o, n, int(math.ceil(6 * o / (min(o, n) * 0.99))))
 
 
 class StreamSet:
@@ -1208,7 +1243,36 @@ class StreamSet:
         self._arena = None
         self._descs = None
 
-    def read(self, stream_ids, starts, length, layout="tc"):
+    def _check_rate(self, sample_rate, streams, who):
+        """sample_rate as an int, after the refusals: {stream's rate: (o, n, W)} for the rates of `streams`."""
+        if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate:
+            raise ValueError("%s: sample_rate must be a whole number" % who)
+        R = int(sample_rate)
+        if not 0 < R < RESAMPLE_RATE_LIMIT:
+            raise ValueError("%s: sample_rate must be 1 .. %d, not %d" % (who, RESAMPLE_RATE_LIMIT - 1, R))
+        pairs = {}
+        for fs in {self.sample_rates[s] for s in streams if self.problems[s] is None}:
+            if not 0 < fs < RESAMPLE_RATE_LIMIT:
+                raise ValueError("%s: a stream's sample rate is %d" % (who, fs))
+            pairs[fs] = o, n, W = resample_pair(fs, R)
+            if n * 2 * W > RESAMPLE_TABLE_LIMIT:
+                raise ValueError("%s: resampling %d Hz to %d Hz needs a coefficient table of %d x %d entries, more than %d"
+                                 % (who, fs, R, n, 2 * W, RESAMPLE_TABLE_LIMIT))
+        return R, pairs
+
+    def lengths_at(self, sample_rate):
+        """Every stream's length in samples per channel after resampling to sample_rate, ceil(T * n / o), as an int64 tensor (0 for a
+        problem stream): what read(..., sample_rate=sample_rate) counts starts and valid against."""
+        import torch
+        R, pairs = self._check_rate(sample_rate, range(len(self)), "lengths_at")
+        out = np.zeros(len(self), dtype=np.int64)
+        for s in range(len(self)):
+            if self.problems[s] is None:
+                o, n, _ = pairs[self.sample_rates[s]]
+                out[s] = (int(self._lengths[s]) * n + o - 1) // o
+        return torch.from_numpy(out)
+
+    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None):
         """A batch of windows: window k is samples [starts[k], starts[k] + length) of stream stream_ids[k], positions counted as load()
         counts them (by cumulative block size in frame order; the frame headers' sample numbers are not consulted).  Returns (float32
         tensor on the context's GPU, contiguous: [B, length, C] for layout "tc", [B, C, length] for "ct"; valid): valid[k] =
@@ -1218,7 +1282,16 @@ class StreamSet:
         multiple of 8 floats; one clx_gather_windows launch then cuts the windows out of it.  Frames shared by overlapping windows are
         decoded once per window.  Raises ValueError for a negative start or length, an unknown stream id or layout, or windows whose
         streams differ in channel count; the stream's `problems` entry when a window names a problem stream; ClaxonError with a
-        failing frame's status and message, " (window k, stream s)" appended.  The result is ready on the current torch stream."""
+        failing frame's status and message, " (window k, stream s)" appended.  The result is ready on the current torch stream.
+
+        With sample_rate=R the windows are read at R Hz whatever rate each stream has: starts and length count samples at R, window k
+        is outputs [starts[k], starts[k] + length) of its stream resampled by the fixed windowed-sinc resampler of
+        clx_resample_windows (claxon_hip.h), zero padding at both ends of the stream, and valid[k] =
+        clamp(lengths_at(R)[s] - starts[k], 0, length).  The frames decoded are those that cover the filter's source span
+        [max(0, floor(m0*o/n) - W + 1), min(T, floor(m1*o/n) + W + 1)) of the window's first and last live output m0 and m1; one
+        clx_resample_windows launch takes the place of the gather.  Streams of different rates may share a call; a window of a stream
+        whose rate is R is the copy that read() without sample_rate gives.  ValueError for a sample_rate that is not 1 .. 2^20 - 1 and
+        for a rate pair whose coefficient table would have more than 2^18 entries (44100 -> 16001)."""
         import torch
         if self._descs is None:
             raise ValueError("read: the stream set is closed")
@@ -1243,15 +1316,28 @@ class StreamSet:
             raise ValueError("read: the windows' streams differ in their channel count (%s)" % sorted(chans))
         ch = chans.pop() if len(chans) == 1 else 0
         B, dev = sid.size, "cuda:%d" % self.ctx.device
-        valid = np.clip(self._lengths[sid] - st, 0, length)
+        if sample_rate is None:
+            valid = np.clip(self._lengths[sid] - st, 0, length)
+        else:
+            R, pairs = self._check_rate(sample_rate, set(sid.tolist()), "read")
+            onw = np.array([pairs[self.sample_rates[s]] for s in sid.tolist()], dtype=np.int64).reshape(-1, 3)
+            o, n, W = onw[:, 0], onw[:, 1], onw[:, 2]
+            valid = np.clip((self._lengths[sid] * n + o - 1) // o - st, 0, length)
         shape = (B, length, ch) if layout == "tc" else (B, ch, length)
         out = torch.empty(shape, dtype=torch.float32, device=dev)
         if B == 0 or length == 0:
             return out, torch.from_numpy(valid)
         live = np.nonzero(valid > 0)[0]
+        # a live window's source span [lo, hi) in its stream's samples: the window itself, or what the filter reaches from it
+        lo, hi = st[live], st[live] + valid[live]
+        if sample_rate is not None:
+            ol, nl, Wl = o[live], n[live], W[live]
+            copy = Wl == 0
+            lo = np.where(copy, lo, np.maximum(lo * ol // nl - Wl + 1, 0))
+            hi = np.where(copy, hi, np.minimum((hi - 1) * ol // nl + Wl + 1, self._lengths[sid[live]]))
         # the covering frames: a searchsorted on the cumulative sample starts (one axis for the whole set: a live window lies inside its stream)
-        f0 = np.searchsorted(self._start, self._base[sid[live]] + st[live], side="right") - 1
-        f1 = np.searchsorted(self._start, self._base[sid[live]] + st[live] + valid[live] - 1, side="right") - 1
+        f0 = np.searchsorted(self._start, self._base[sid[live]] + lo, side="right") - 1
+        f1 = np.searchsorted(self._start, self._base[sid[live]] + hi - 1, side="right") - 1
         cnt = f1 - f0 + 1
         ends = np.cumsum(cnt)
         rows = np.repeat(f0 - (ends - cnt), cnt) + np.arange(int(ends[-1]) if live.size else 0)
@@ -1260,7 +1346,7 @@ class StreamSet:
         base = np.cumsum(room) - room
         out_offs = np.repeat(base - self._start[f0] * ch, cnt) + self._start[rows] * ch
         src_first = np.zeros(B, dtype=np.uint64)
-        src_first[live] = base + (st[live] - self._local[f0]) * ch
+        src_first[live] = base + (lo - self._local[f0]) * ch
         scratch = torch.empty(max(int(room.sum()), 8), dtype=torch.float32, device=dev)
         if rows.size:
             res = _decode_f32(self.ctx, self._arena, self._arena_len, self._descs[rows], out_offs.astype(np.uint64), scratch)
@@ -1269,7 +1355,14 @@ class StreamSet:
             if bad.size:
                 k = int(live[int(np.searchsorted(ends, int(bad[0]), side="right"))])
                 _raise_first_failure(res, " (window %d, stream %d)" % (k, int(sid[k])))
-        self.ctx.gather_windows(scratch, src_first, valid, length, ch, _LAYOUTS[layout], out)
+        if sample_rate is None:
+            self.ctx.gather_windows(scratch, src_first, valid, length, ch, _LAYOUTS[layout], out)
+        else:
+            src_t0, src_n = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.uint32)
+            src_t0[live], src_n[live] = lo, hi - lo
+            rates = np.array([self.sample_rates[s] for s in sid.tolist()], dtype=np.uint32)
+            self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
+                                      _LAYOUTS[layout], out)
         return out, torch.from_numpy(valid)
 
 

@@ -11,6 +11,7 @@
 #include "clx_md5.hip"
 #include "clx_index.hip"
 #include "clx_window.hip"
+#include "clx_resample.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -255,6 +256,15 @@ struct clx_ctx {
     clx_win_job* d_win = nullptr; clx_win_job* h_win = nullptr; size_t win_cap = 0;
     std::vector<void*> win_old_dev, win_old_host;
     hipEvent_t ev_win_up = nullptr, ev_win_done = nullptr; bool win_used = false;
+    // scratch of clx_resample_windows, by the same rules: one table of the call's jobs followed by its rate pairs (rs_cap bytes, on
+    // the device and in pinned staging), and the coefficient tables of every rate pair the context has met (rs_cache: the host copy;
+    // d_rs_coef: the first rs_coef_up floats of it).  A pair's table is written once, behind those in use, so an earlier launch
+    // never reads what an upload writes; a coefficient buffer that has to grow is replaced like a job table (rs_old_dev).
+    void* d_rs = nullptr; void* h_rs = nullptr; size_t rs_cap = 0;
+    clx_rs_cache rs_cache; float* d_rs_coef = nullptr; size_t rs_coef_cap = 0, rs_coef_up = 0;
+    std::vector<uint32_t> rs_call_fs;
+    std::vector<void*> rs_old_dev, rs_old_host;
+    hipEvent_t ev_rs_up = nullptr, ev_rs_done = nullptr; bool rs_used = false;
 };
 
 // K2 build by batch size (groups of 64 predictor slots) unless CLX_K2_LATENCY / CLX_K2_THROUGHPUT force one
@@ -420,6 +430,12 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->win_old_dev.push_back(ctx->d_win); ctx->win_old_host.push_back(ctx->h_win);
     for (void* p : ctx->win_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->win_old_host) if (p) (void)hipHostFree(p);
+    if (ctx->rs_used) (void)hipEventSynchronize(ctx->ev_rs_done);
+    if (ctx->ev_rs_up) (void)hipEventDestroy(ctx->ev_rs_up);
+    if (ctx->ev_rs_done) (void)hipEventDestroy(ctx->ev_rs_done);
+    ctx->rs_old_dev.push_back(ctx->d_rs); ctx->rs_old_dev.push_back(ctx->d_rs_coef); ctx->rs_old_host.push_back(ctx->h_rs);
+    for (void* p : ctx->rs_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->rs_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1444,6 +1460,60 @@ extern "C" int clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_
                        (const clx_win_job*)ctx->d_win, n_tiles, window_len, channels, layout, (uint32_t*)d_out);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_win_done, stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
+                                    const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, size_t n_windows, uint32_t out_rate,
+                                    uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    uint32_t n_tiles = 0;
+    const char* why = clx_resample_plan(ctx->rs_cache, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, n_windows, out_rate, window_len,
+                                        channels, layout, d_out, &ctx->rs_call_fs, &n_tiles);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_rs_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rs_up, hipEventDisableTiming));
+    if (!ctx->ev_rs_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rs_done, hipEventDisableTiming));
+    const size_t n_rates = 1 + ctx->rs_call_fs.size();
+    const size_t bytes = n_windows * sizeof(clx_rs_job) + n_rates * sizeof(clx_rs_rate);       // (the jobs, then the rate pairs: both 8-byte aligned)
+    if (bytes > ctx->rs_cap) {                                 // a larger table, before anything is queued; the old one is not freed here
+        const size_t want = bytes + bytes / 2 + 4096;
+        void* d = nullptr; void* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&d, want), "hipMalloc resample table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc(&h, want, hipHostMallocDefault), "hipHostMalloc resample table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_rs) { ctx->rs_old_dev.push_back(ctx->d_rs); ctx->rs_old_host.push_back(ctx->h_rs); }
+        ctx->d_rs = d; ctx->h_rs = h; ctx->rs_cap = want;
+    } else if (ctx->rs_used) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_rs_up));      // (the upload only: the earlier launch itself is not waited for)
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_rs_done, 0));
+    }
+    clx_rs_job* h_jobs = (clx_rs_job*)ctx->h_rs;
+    clx_rs_rate* h_rates = (clx_rs_rate*)(h_jobs + n_windows);
+    clx_resample_fill(&ctx->rs_cache, h_jobs, h_rates, ctx->rs_call_fs, src_first, src_t0, src_n, out_t0, valid, src_rate, n_windows, out_rate);
+    // the tables of the pairs this call met first: behind the ones on the device already, in a larger buffer when they do not fit
+    const std::vector<float>& coef = ctx->rs_cache.coef;
+    if (coef.size() > ctx->rs_coef_cap) {
+        const size_t want = coef.size() + coef.size() / 2 + 4096;
+        float* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(float)), "hipMalloc resample coefficients")) return CLX_API_ERROR;
+        if (ctx->d_rs_coef) ctx->rs_old_dev.push_back(ctx->d_rs_coef);
+        ctx->d_rs_coef = d; ctx->rs_coef_cap = want; ctx->rs_coef_up = 0;
+    }
+    if (coef.size() > ctx->rs_coef_up) {
+        HIP_TRY(ctx, hipMemcpy(ctx->d_rs_coef + ctx->rs_coef_up, coef.data() + ctx->rs_coef_up, (coef.size() - ctx->rs_coef_up) * sizeof(float),
+                               hipMemcpyHostToDevice));
+        ctx->rs_coef_up = coef.size();
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rs, ctx->h_rs, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_rs_up, stream));
+    ctx->rs_used = true;                                       // (from here on the staging and the table are in use)
+    const clx_rs_job* d_jobs = (const clx_rs_job*)ctx->d_rs;
+    hipLaunchKernelGGL(clx_k_resample, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_rs::kThreads), 0, stream, (const float*)d_src, d_jobs,
+                       (const clx_rs_rate*)(d_jobs + n_windows), (const float*)ctx->d_rs_coef, n_tiles, window_len, channels, layout, (float*)d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_rs_done, stream));
     return CLX_OK;
 }
 

@@ -404,6 +404,28 @@ enum { CLX_WINDOW_TC = 0, CLX_WINDOW_CT = 1 };
 int  clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const uint32_t* valid,
                         size_t n_windows, uint32_t window_len, uint32_t channels, uint32_t layout,
                         void* d_out, void* stream);
+/* clx_gather_windows at a target sample rate: a dense batch of fixed-length windows of the audio resampled to `out_rate`, computed
+ * while they are cut out of d_src, in one launch (clx_k_resample).  The resampler is fixed and has no tunables: band-limited
+ * interpolation with a Hann-windowed sinc, filter width 6 and rolloff 0.99 (torchaudio.functional.resample's defaults).  For
+ * fs = src_rate[k]: g = gcd(fs, out_rate), o = fs / g, n = out_rate / g, base = min(o, n) * 0.99, W = ceil(6 * o / base), and
+ *   y[m] = sum over s of x[s] * h(s - m*o/n),   h(d) = sinc(t) * cos^2(pi*t/12) * base/o with t = d*base/o, 0 where |t| >= 6,
+ * x = 0 outside the stream; only the 2W taps s = floor(m*o/n) - W + 1 + k, k = 0 .. 2W - 1, can be non-zero.  The coefficients are
+ * computed in double, rounded once to float32 and kept on the context, one table per (o, n); the kernel accumulates in float32,
+ * taps in ascending order.  d_src is channel-interleaved float32 as for clx_gather_windows.  Window k's source span is the src_n[k]
+ * samples per channel from float index src_first[k] on, the first of them stream sample src_t0[k]; a tap outside
+ * [src_t0[k], src_t0[k] + src_n[k]) counts as zero, and no float of d_src outside [src_first[k], src_first[k] + src_n[k]*channels)
+ * is read.  The window is outputs out_t0[k] .. out_t0[k] + valid[k] - 1 of the resampled stream, then zeros up to window_len, laid
+ * out as CLX_WINDOW_TC / CLX_WINDOW_CT: the call writes all of d_out.  Where src_rate[k] == out_rate the window is a plain copy
+ * (output m is source sample m, bit for bit), not a pass through a filter; one call may mix rates and copies.  The host arrays are
+ * copied before the call returns into scratch that the context owns (grown, when it must, before anything is queued; released by
+ * clx_destroy).  Asynchronous on `stream` like clx_gather_windows, except that the first call with a new rate pair uploads its
+ * table with a synchronous copy.  CLX_API_ERROR (clx_last_error says why) for a null pointer while n_windows * window_len > 0,
+ * channels outside 1..8, an unknown layout, a valid[k] above window_len, a rate of 0 or >= 2^20 (the width of STREAMINFO's field),
+ * a rate pair whose [n][2W] table would have more than 2^18 entries (44100 -> 16001), an out_t0[k] of 2^43 or more, or too many
+ * windows for one grid; n_windows == 0 or window_len == 0 succeeds and launches nothing. */
+int  clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
+                          const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, size_t n_windows,
+                          uint32_t out_rate, uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
