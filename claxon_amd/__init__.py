@@ -99,13 +99,13 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
-    "clx_resample_windows",
+    "clx_resample_windows", "clx_mix_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -180,6 +180,7 @@ def lib():
     L.clx_md5_streams.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, sz, vp, vp]
     L.clx_gather_windows.argtypes = [vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_resample_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    L.clx_mix_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -677,6 +678,29 @@ class Context:
         ptr = [t.data_ptr() if hasattr(t, "data_ptr") else (int(t) if t else None) for t in (src, out)]
         self._check(lib().clx_resample_windows(self._h, ptr[0], *[_np_ptr(a) for a in arrs], arrs[0].size, int(out_rate), int(window_len),
                                                int(channels), int(layout), ptr[1], C.c_void_p(handle) if handle else None))
+        return out
+
+    def mix_windows(self, src, src_first, src_t0, src_n, out_t0, valid, src_rate, src_channels, out_rate, window_len, out_channels, layout,
+                    out, stream=None):
+        """clx_mix_windows: resample_windows with window k's source holding src_channels[k] interleaved channels and every window brought
+        to out_channels: unchanged where the two are equal, the float32 mean of the channels (claxon_hip.h gives its order) for
+        out_channels == 1, a mono source copied to every channel; any other combination is refused.  `out` is [B, L, out_channels]
+        (WINDOW_TC) or [B, out_channels, L] (WINDOW_CT).  Everything else as for resample_windows."""
+        arrs = [np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in ((src_first, np.uint64), (src_t0, np.int64), (src_n, np.uint32),
+                                                                           (out_t0, np.uint64), (valid, np.uint32), (src_rate, np.uint32),
+                                                                           (src_channels, np.uint8))]
+        if len({a.size for a in arrs}) != 1:
+            raise ValueError("mix_windows: the per-window arrays differ in length")
+        for name, v in (("out_rate", out_rate), ("window_len", window_len), ("out_channels", out_channels), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("mix_windows: %s is out of range" % name)
+        if stream is None and hasattr(out, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(out.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        ptr = [t.data_ptr() if hasattr(t, "data_ptr") else (int(t) if t else None) for t in (src, out)]
+        self._check(lib().clx_mix_windows(self._h, ptr[0], *[_np_ptr(a) for a in arrs], arrs[0].size, int(out_rate), int(window_len),
+                                          int(out_channels), int(layout), ptr[1], C.c_void_p(handle) if handle else None))
         return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -1272,7 +1296,7 @@ class StreamSet:
                 out[s] = (int(self._lengths[s]) * n + o - 1) // o
         return torch.from_numpy(out)
 
-    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None):
+    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None):
         """A batch of windows: window k is samples [starts[k], starts[k] + length) of stream stream_ids[k], positions counted as load()
         counts them (by cumulative block size in frame order; the frame headers' sample numbers are not consulted).  Returns (float32
         tensor on the context's GPU, contiguous: [B, length, C] for layout "tc", [B, C, length] for "ct"; valid): valid[k] =
@@ -1291,7 +1315,15 @@ class StreamSet:
         [max(0, floor(m0*o/n) - W + 1), min(T, floor(m1*o/n) + W + 1)) of the window's first and last live output m0 and m1; one
         clx_resample_windows launch takes the place of the gather.  Streams of different rates may share a call; a window of a stream
         whose rate is R is the copy that read() without sample_rate gives.  ValueError for a sample_rate that is not 1 .. 2^20 - 1 and
-        for a rate pair whose coefficient table would have more than 2^18 entries (44100 -> 16001)."""
+        for a rate pair whose coefficient table would have more than 2^18 entries (44100 -> 16001).
+
+        With channels=K (1..8) every window has K channels whatever its stream has -- the result is [B, length, K] / [B, K, length] --
+        and streams of different channel counts share the call: a stream of K channels is read as ever, a multi-channel stream is
+        averaged to K == 1 (the float32 mean of clx_mix_windows, claxon_hip.h; before the resampler when sample_rate is given) and a
+        mono stream is copied to each of the K channels.  valid, the frames decoded, the plan and the run do not change; where some
+        window's stream has another count than K, one clx_mix_windows launch takes the place of the gather or the resampler.
+        ValueError for a K that is not a whole number in 1..8 and for a window whose stream has neither K channels nor one, with K not
+        1."""
         import torch
         if self._descs is None:
             raise ValueError("read: the stream set is closed")
@@ -1311,10 +1343,22 @@ class StreamSet:
         for s in sid.tolist():
             if self.problems[s] is not None:
                 raise self.problems[s]
-        chans = {self.channels[s] for s in set(sid.tolist())} or {c for c, p in zip(self.channels, self.problems) if p is None}
-        if len(chans) > 1 and sid.size:
-            raise ValueError("read: the windows' streams differ in their channel count (%s)" % sorted(chans))
-        ch = chans.pop() if len(chans) == 1 else 0
+        cw = np.array([self.channels[s] for s in sid.tolist()], dtype=np.int64)         # each window's stream's channel count
+        if channels is None:
+            chans = {self.channels[s] for s in set(sid.tolist())} or {c for c, p in zip(self.channels, self.problems) if p is None}
+            if len(chans) > 1 and sid.size:
+                raise ValueError("read: the windows' streams differ in their channel count (%s)" % sorted(chans))
+            ch = chans.pop() if len(chans) == 1 else 0
+        else:
+            if isinstance(channels, bool) or not isinstance(channels, (int, float, np.integer, np.floating)) or int(channels) != channels \
+                    or not 1 <= int(channels) <= 8:
+                raise ValueError("read: channels must be a whole number in 1..8, not %r" % (channels,))
+            ch = int(channels)
+            odd = np.nonzero((cw != ch) & (cw != 1) & (ch != 1))[0]
+            if odd.size:
+                k = int(odd[0])
+                raise ValueError("read: no rule brings the %d channels of stream %d to %d (window %d)" % (int(cw[k]), int(sid[k]), ch, k))
+        mixed = bool(np.any(cw != ch))                       # (only with channels=K: some window is reduced or replicated)
         B, dev = sid.size, "cuda:%d" % self.ctx.device
         if sample_rate is None:
             valid = np.clip(self._lengths[sid] - st, 0, length)
@@ -1335,18 +1379,19 @@ class StreamSet:
             copy = Wl == 0
             lo = np.where(copy, lo, np.maximum(lo * ol // nl - Wl + 1, 0))
             hi = np.where(copy, hi, np.minimum((hi - 1) * ol // nl + Wl + 1, self._lengths[sid[live]]))
+        cl = cw[live]
         # the covering frames: a searchsorted on the cumulative sample starts (one axis for the whole set: a live window lies inside its stream)
         f0 = np.searchsorted(self._start, self._base[sid[live]] + lo, side="right") - 1
         f1 = np.searchsorted(self._start, self._base[sid[live]] + hi - 1, side="right") - 1
         cnt = f1 - f0 + 1
         ends = np.cumsum(cnt)
         rows = np.repeat(f0 - (ends - cnt), cnt) + np.arange(int(ends[-1]) if live.size else 0)
-        span = (self._start[f1] + self._descs["block_size"][f1].astype(np.int64) - self._start[f0]) * ch      # floats of a window's frames
+        span = (self._start[f1] + self._descs["block_size"][f1].astype(np.int64) - self._start[f0]) * cl      # floats of a window's frames
         room = (span + 7) // 8 * 8
         base = np.cumsum(room) - room
-        out_offs = np.repeat(base - self._start[f0] * ch, cnt) + self._start[rows] * ch
+        out_offs = np.repeat(base - self._start[f0] * cl, cnt) + self._start[rows] * np.repeat(cl, cnt)
         src_first = np.zeros(B, dtype=np.uint64)
-        src_first[live] = base + (lo - self._local[f0]) * ch
+        src_first[live] = base + (lo - self._local[f0]) * cl
         scratch = torch.empty(max(int(room.sum()), 8), dtype=torch.float32, device=dev)
         if rows.size:
             res = _decode_f32(self.ctx, self._arena, self._arena_len, self._descs[rows], out_offs.astype(np.uint64), scratch)
@@ -1355,14 +1400,21 @@ class StreamSet:
             if bad.size:
                 k = int(live[int(np.searchsorted(ends, int(bad[0]), side="right"))])
                 _raise_first_failure(res, " (window %d, stream %d)" % (k, int(sid[k])))
-        if sample_rate is None:
+        if sample_rate is None and not mixed:
             self.ctx.gather_windows(scratch, src_first, valid, length, ch, _LAYOUTS[layout], out)
         else:
             src_t0, src_n = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.uint32)
             src_t0[live], src_n[live] = lo, hi - lo
-            rates = np.array([self.sample_rates[s] for s in sid.tolist()], dtype=np.uint32)
-            self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
-                                      _LAYOUTS[layout], out)
+            if sample_rate is None:                          # (mixed at the native rate: every window a copy, "rate 1 to rate 1")
+                rates, R = np.ones(B, dtype=np.uint32), 1
+            else:
+                rates = np.array([self.sample_rates[s] for s in sid.tolist()], dtype=np.uint32)
+            if mixed:
+                self.ctx.mix_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, cw, R, length, ch,
+                                     _LAYOUTS[layout], out)
+            else:
+                self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
+                                          _LAYOUTS[layout], out)
         return out, torch.from_numpy(valid)
 
 

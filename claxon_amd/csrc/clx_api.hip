@@ -11,7 +11,7 @@
 #include "clx_md5.hip"
 #include "clx_index.hip"
 #include "clx_window.hip"
-#include "clx_resample.hip"
+#include "clx_mix.hip"                  // (brings clx_resample.hip with it)
 
 #include <algorithm>
 #include <cstdio>
@@ -256,7 +256,7 @@ struct clx_ctx {
     clx_win_job* d_win = nullptr; clx_win_job* h_win = nullptr; size_t win_cap = 0;
     std::vector<void*> win_old_dev, win_old_host;
     hipEvent_t ev_win_up = nullptr, ev_win_done = nullptr; bool win_used = false;
-    // scratch of clx_resample_windows, by the same rules: one table of the call's jobs followed by its rate pairs (rs_cap bytes, on
+    // scratch of clx_resample_windows and clx_mix_windows (one set for both), by the same rules: one table of the call's jobs followed by its rate pairs (rs_cap bytes, on
     // the device and in pinned staging), and the coefficient tables of every rate pair the context has met (rs_cache: the host copy;
     // d_rs_coef: the first rs_coef_up floats of it).  A pair's table is written once, behind those in use, so an earlier launch
     // never reads what an upload writes; a coefficient buffer that has to grow is replaced like a job table (rs_old_dev).
@@ -1463,15 +1463,11 @@ extern "C" int clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_
     return CLX_OK;
 }
 
-extern "C" int clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
-                                    const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, size_t n_windows, uint32_t out_rate,
-                                    uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream_) {
-    if (!ctx) return CLX_API_ERROR;
-    uint32_t n_tiles = 0;
-    const char* why = clx_resample_plan(ctx->rs_cache, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, n_windows, out_rate, window_len,
-                                        channels, layout, d_out, &ctx->rs_call_fs, &n_tiles);
-    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
-    if (n_tiles == 0) return CLX_OK;
+// What clx_resample_windows and clx_mix_windows share behind their plans: the scratch, the tables and the launch.  src_channels is
+// nullptr for clx_resample_windows (clx_k_resample, `channels` everywhere), else clx_mix_windows' (clx_k_mix, `channels` out).
+static int clx_rs_submit(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
+                         const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, const uint8_t* src_channels, size_t n_windows,
+                         uint32_t out_rate, uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream_, uint32_t n_tiles) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
     if (!ctx->ev_rs_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rs_up, hipEventDisableTiming));
@@ -1491,7 +1487,10 @@ extern "C" int clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint6
     }
     clx_rs_job* h_jobs = (clx_rs_job*)ctx->h_rs;
     clx_rs_rate* h_rates = (clx_rs_rate*)(h_jobs + n_windows);
-    clx_resample_fill(&ctx->rs_cache, h_jobs, h_rates, ctx->rs_call_fs, src_first, src_t0, src_n, out_t0, valid, src_rate, n_windows, out_rate);
+    if (src_channels)
+        clx_mix_fill(&ctx->rs_cache, h_jobs, h_rates, ctx->rs_call_fs, src_first, src_t0, src_n, out_t0, valid, src_rate, src_channels, n_windows, out_rate);
+    else
+        clx_resample_fill(&ctx->rs_cache, h_jobs, h_rates, ctx->rs_call_fs, src_first, src_t0, src_n, out_t0, valid, src_rate, n_windows, out_rate);
     // the tables of the pairs this call met first: behind the ones on the device already, in a larger buffer when they do not fit
     const std::vector<float>& coef = ctx->rs_cache.coef;
     if (coef.size() > ctx->rs_coef_cap) {
@@ -1510,11 +1509,42 @@ extern "C" int clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint6
     HIP_TRY(ctx, hipEventRecord(ctx->ev_rs_up, stream));
     ctx->rs_used = true;                                       // (from here on the staging and the table are in use)
     const clx_rs_job* d_jobs = (const clx_rs_job*)ctx->d_rs;
-    hipLaunchKernelGGL(clx_k_resample, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_rs::kThreads), 0, stream, (const float*)d_src, d_jobs,
-                       (const clx_rs_rate*)(d_jobs + n_windows), (const float*)ctx->d_rs_coef, n_tiles, window_len, channels, layout, (float*)d_out);
+    if (src_channels)
+        hipLaunchKernelGGL(clx_k_mix, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_rs::kThreads), 0, stream, (const float*)d_src, d_jobs,
+                           (const clx_rs_rate*)(d_jobs + n_windows), (const float*)ctx->d_rs_coef, n_tiles, window_len, channels, layout, (float*)d_out);
+    else
+        hipLaunchKernelGGL(clx_k_resample, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_rs::kThreads), 0, stream, (const float*)d_src, d_jobs,
+                           (const clx_rs_rate*)(d_jobs + n_windows), (const float*)ctx->d_rs_coef, n_tiles, window_len, channels, layout, (float*)d_out);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_rs_done, stream));
     return CLX_OK;
+}
+
+extern "C" int clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
+                                    const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, size_t n_windows, uint32_t out_rate,
+                                    uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    uint32_t n_tiles = 0;
+    const char* why = clx_resample_plan(ctx->rs_cache, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, n_windows, out_rate, window_len,
+                                        channels, layout, d_out, &ctx->rs_call_fs, &n_tiles);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (n_tiles == 0) return CLX_OK;
+    return clx_rs_submit(ctx, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, nullptr, n_windows, out_rate, window_len, channels, layout,
+                         d_out, stream_, n_tiles);
+}
+
+// (the job table, its staging and its two events are clx_resample_windows' own: the two calls follow each other under the same rules)
+extern "C" int clx_mix_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
+                               const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, const uint8_t* src_channels, size_t n_windows,
+                               uint32_t out_rate, uint32_t window_len, uint32_t out_channels, uint32_t layout, void* d_out, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    uint32_t n_tiles = 0;
+    const std::string why = clx_mix_plan(ctx->rs_cache, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, src_channels, n_windows, out_rate,
+                                         window_len, out_channels, layout, d_out, &ctx->rs_call_fs, &n_tiles);
+    if (!why.empty()) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (n_tiles == 0) return CLX_OK;
+    return clx_rs_submit(ctx, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, src_channels, n_windows, out_rate, window_len, out_channels,
+                         layout, d_out, stream_, n_tiles);
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

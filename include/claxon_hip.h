@@ -426,6 +426,26 @@ int  clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_fir
 int  clx_resample_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
                           const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, size_t n_windows,
                           uint32_t out_rate, uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream);
+/* clx_resample_windows with every window brought to out_channels (K, 1..8) channels while it is cut, in one launch (clx_k_mix): one
+ * dense [B, L, K] / [B, K, L] batch from streams that differ in channel count as well as in rate.  src_channels[k] (Cs, 1..8, a
+ * host array) is the channel count of window k's source: its span is src_n[k] samples of Cs interleaved floats from float
+ * src_first[k] on, and no float outside [src_first[k], src_first[k] + src_n[k]*Cs) is read.  One of three rules applies:
+ *   identity   Cs == K       exactly what clx_gather_windows / clx_resample_windows give, bit for bit;
+ *   reduce     K == 1 < Cs   the mean of the channels in float32, in this order: s = x[t][0]; s = s + x[t][1]; ...;
+ *                            s = s + x[t][Cs-1], each add rounded to nearest, then s * r with r the float32 nearest to 1/Cs;
+ *   replicate  Cs == 1 < K   the mono sample goes to each of the K channels.
+ * Any other (Cs, K) is refused: there is no one downmix matrix everybody expects.  Where src_rate[k] == out_rate the window is
+ * that mix of source samples out_t0[k] .. (identity and replicate move 32-bit words).  Otherwise the mix comes first and the
+ * resampler of clx_resample_windows is applied to the mixed float32 signal: a tap outside the span counts as zero and none of its
+ * Cs floats is loaded, the sum runs in float32, taps ascending, one fmaf each with the mixed value as the multiplicand; replicated
+ * channels are bitwise equal.  The call writes all of d_out, +0.0 from valid[k] on.  Rate pairs and their tables are shared with
+ * clx_resample_windows (a pair built by either call serves both), and so are the scratch, the stream rules and every refusal;
+ * CLX_API_ERROR also for out_channels or a src_channels[k] outside 1..8 and for a (Cs, K) that no rule covers.  n_windows == 0 or
+ * window_len == 0 succeeds and launches nothing. */
+int  clx_mix_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first, const int64_t* src_t0, const uint32_t* src_n,
+                     const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, const uint8_t* src_channels,
+                     size_t n_windows, uint32_t out_rate, uint32_t window_len, uint32_t out_channels, uint32_t layout, void* d_out,
+                     void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
