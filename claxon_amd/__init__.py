@@ -32,6 +32,7 @@ OUT_PCM24 = 32768           # the same with packed 24-bit samples (3 bytes each)
 OUT_F32 = 65536             # the same with channel-interleaved float32 normalized to [-1, 1): (float)v * 2^-(bps-1), 4 bytes per sample
 SAMPLE_F32 = 0x104          # sample format of interleave / decode_frames_stream: the floats of OUT_F32 (next to sample_bytes 1..4)
 WINDOW_TC, WINDOW_CT = 0, 1   # clx_gather_windows layouts: [B, L, C] and [B, C, L]
+MEL_POWER, MEL_LN, MEL_LOG10 = 0, 1, 2   # clx_mel_create modes
 SUBMIT_DEPTH = 24           # CLX_SUBMIT_DEPTH: the most submissions a Batch keeps in flight (Batch.submit_depth: this batch's)
 
 
@@ -99,13 +100,13 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
-    "clx_resample_windows", "clx_mix_windows",
+    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_destroy", "clx_mel_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -181,6 +182,10 @@ def lib():
     L.clx_gather_windows.argtypes = [vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_resample_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_mix_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    L.clx_mel_create.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(vp)]
+    L.clx_mel_destroy.argtypes = [vp, vp]
+    L.clx_mel_destroy.restype = None
+    L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -703,6 +708,35 @@ class Context:
                                           int(out_channels), int(layout), ptr[1], C.c_void_p(handle) if handle else None))
         return out
 
+    def mel_windows(self, spec, audio, valid, n_frames, layout, out, stream=None):
+        """clx_mel_windows: the features of `spec` (a MelSpec of this context) for the dense mono batch `audio` [B, L] (float32, the
+        samples from valid[k] on zero), n_frames frames per window, written to `out` as [B, n_frames, n_mels] (WINDOW_TC) or
+        [B, n_mels, n_frames] (WINDOW_CT); a frame from ceil(valid[k] / hop) on is zeros.  `audio` and `out` are CUDA float32 tensors
+        (B and L are the tensor's) or `audio` is a (pointer, B, L) triple and `out` a pointer.  Asynchronous on `stream` as
+        gather_windows is."""
+        if getattr(spec, "_h", None) is None or spec.ctx is not self:
+            raise ValueError("mel_windows: the spec is closed or belongs to another context")
+        if hasattr(audio, "data_ptr"):
+            if audio.dim() != 2 or not audio.is_contiguous():
+                raise ValueError("mel_windows: audio must be a contiguous [B, L] tensor")
+            a_ptr, B, L = audio.data_ptr(), int(audio.shape[0]), int(audio.shape[1])
+        else:
+            a_ptr, B, L = (int(audio[0]) if audio[0] else None), int(audio[1]), int(audio[2])
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("mel_windows: valid has %d entries for %d windows" % (valid.size, B))
+        for name, v in (("window_len", L), ("n_frames", n_frames), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("mel_windows: %s is out of range" % name)
+        if stream is None and hasattr(out, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(out.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
+        self._check(lib().clx_mel_windows(self._h, spec._h, a_ptr, B, L, _np_ptr(valid), int(n_frames), int(layout), o_ptr,
+                                          C.c_void_p(handle) if handle else None))
+        return out
+
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
         a = _u8(arena)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -1204,6 +1238,111 @@ def verify(ctx, streams):
     return verdicts
 
 
+# ---- mel features ---------------------------------------------------------------------------------------------------------------------
+
+_MEL_MODES = {"power": MEL_POWER, "ln": MEL_LN, "log10": MEL_LOG10}
+
+
+def _hz_to_mel(f, scale):
+    f = np.asarray(f, dtype=np.float64)
+    if scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    lin = f / (200.0 / 3.0)                                  # Slaney: linear below 1 kHz, logarithmic above (27 steps to 6.4 kHz)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (math.log(6.4) / 27.0), lin)
+
+
+def _mel_to_hz(m, scale):
+    m = np.asarray(m, dtype=np.float64)
+    if scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m >= 15.0, 1000.0 * np.exp((math.log(6.4) / 27.0) * (np.maximum(m, 15.0) - 15.0)), m * (200.0 / 3.0))
+
+
+def mel_window(n_fft):
+    """The periodic Hann window of n_fft points: 0.5 - 0.5 cos(2 pi n / n_fft) in double, rounded once to float32."""
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(n_fft), dtype=np.float64) / int(n_fft))).astype(np.float32)
+
+
+def mel_fbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None, mel_scale="htk", norm=None):
+    """The triangular filterbank [n_mels, n_fft // 2 + 1] (float32, built in double and rounded once): n_mels + 2 points evenly
+    spaced on the mel scale from f_min to f_max (default sample_rate / 2), band m rising from point m to point m + 1 and falling to
+    point m + 2, sampled at the bins' frequencies j * sample_rate / n_fft; norm="slaney" scales band m by 2 / (f[m + 2] - f[m]).
+    ValueError for a band without a single non-zero bin (too many bands for n_fft), naming it."""
+    if mel_scale not in ("htk", "slaney"):
+        raise ValueError("mel_fbank: mel_scale must be 'htk' or 'slaney', not %r" % (mel_scale,))
+    if norm not in (None, "slaney"):
+        raise ValueError("mel_fbank: norm must be None or 'slaney', not %r" % (norm,))
+    sample_rate, n_fft, n_mels = float(sample_rate), int(n_fft), int(n_mels)
+    f_max = sample_rate / 2.0 if f_max is None else float(f_max)
+    f_min = float(f_min)
+    if not (sample_rate > 0 and 0.0 <= f_min < f_max <= sample_rate / 2.0):
+        raise ValueError("mel_fbank: need sample_rate > 0 and 0 <= f_min < f_max <= sample_rate / 2")
+    if n_fft < 2 or n_mels < 1:
+        raise ValueError("mel_fbank: need n_fft >= 2 and n_mels >= 1")
+    J = n_fft // 2 + 1
+    freqs = np.arange(J, dtype=np.float64) * (sample_rate / n_fft)
+    pts = _mel_to_hz(np.linspace(_hz_to_mel(f_min, mel_scale), _hz_to_mel(f_max, mel_scale), n_mels + 2), mel_scale)
+    diff = pts[1:] - pts[:-1]
+    slopes = pts[:, None] - freqs[None, :]                   # [n_mels + 2, J]
+    down = -slopes[:-2] / diff[:-1, None]
+    up = slopes[2:] / diff[1:, None]
+    fb = np.maximum(0.0, np.minimum(down, up)) + 0.0         # (+ 0.0: no -0.0 in the table)
+    if norm == "slaney":
+        fb = fb * (2.0 / (pts[2:] - pts[:-2]))[:, None]
+    fb = np.ascontiguousarray(fb.astype(np.float32))
+    empty = np.nonzero(~np.any(fb != 0, axis=1))[0]
+    if empty.size:
+        raise ValueError("mel_fbank: band %d (%.1f .. %.1f Hz) has no bin of the %d-point transform at %g Hz"
+                         % (int(empty[0]), pts[empty[0]], pts[empty[0] + 2], n_fft, sample_rate))
+    return fb
+
+
+class MelSpec:
+    """A feature spec for Context.mel_windows and StreamSet.read_mel (clx_mel_create, claxon_hip.h): frames of n_fft samples every
+    `hop`, the periodic Hann window (.window), a triangular mel filterbank (.fbank, [n_mels, n_fft // 2 + 1]: mel_fbank) and the last
+    step -- mode "power" (the band sums), "ln" or "log10" (the logarithm of max(band sum, floor)).  Both tables are built with
+    numpy in double and rounded once to float32.  The spec owns the library's handle (the DFT basis is built and uploaded here,
+    once) until close().  ctx=None builds the tables only.  ValueError for arguments out of range and for a filterbank with an empty
+    band."""
+
+    def __init__(self, ctx, sample_rate, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, mode="ln",
+                 floor=1e-10):
+        self.ctx, self._h = ctx, None
+        for name, v in (("sample_rate", sample_rate), ("n_fft", n_fft), ("hop", hop), ("n_mels", n_mels)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v:
+                raise ValueError("MelSpec: %s must be a whole number, not %r" % (name, v))
+        if mode not in _MEL_MODES:
+            raise ValueError("MelSpec: mode must be 'ln', 'log10' or 'power', not %r" % (mode,))
+        self.sample_rate, self.n_fft, self.hop, self.n_mels = int(sample_rate), int(n_fft), int(hop), int(n_mels)
+        if not 2 <= self.n_fft <= 2048 or not 1 <= self.hop < 1 << 32 or not 1 <= self.n_mels <= 256 or self.sample_rate < 1:
+            raise ValueError("MelSpec: need n_fft in 2..2048, hop >= 1, n_mels in 1..256 and sample_rate >= 1")
+        self.mode, self.floor = mode, float(np.float32(floor))
+        if mode != "power" and not self.floor > 0:
+            raise ValueError("MelSpec: floor must be greater than 0 in mode %r" % mode)
+        self.window = mel_window(self.n_fft)
+        self.fbank = mel_fbank(self.sample_rate, self.n_fft, self.n_mels, f_min, f_max, mel_scale, norm)
+        if ctx is not None:
+            h = C.c_void_p(None)
+            ctx._check(lib().clx_mel_create(ctx._h, self.n_fft, self.hop, _np_ptr(self.window), _np_ptr(self.fbank), self.n_mels,
+                                            _MEL_MODES[mode], self.floor, C.byref(h)))
+            self._h = h
+
+    def window_len(self, n_frames):
+        """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame)."""
+        return (int(n_frames) - 1) * self.hop + self.n_fft if int(n_frames) > 0 else 0
+
+    def close(self):
+        if self._h is not None and self.ctx is not None and self.ctx._h:
+            lib().clx_mel_destroy(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- sample windows from resident streams -----------------------------------------------------------------------------------------
 
 _LAYOUTS = {"tc": WINDOW_TC, "ct": WINDOW_CT}
@@ -1416,6 +1555,32 @@ class StreamSet:
                 self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
                                           _LAYOUTS[layout], out)
         return out, torch.from_numpy(valid)
+
+
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct"):
+        """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
+        starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
+        read(stream_ids, starts, (n_frames - 1) * hop + n_fft, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its
+        frames decoded -- followed by one clx_mel_windows launch on that [B, L] batch.  Returns (float32 tensor on the context's GPU:
+        [B, n_mels, n_frames] for layout "ct", [B, n_frames, n_mels] for "tc"; valid_frames): valid_frames[k] (int64 tensor) =
+        min(ceil(valid[k] / hop), n_frames) with valid[k] the window's samples inside its stream; a frame from there on is zeros,
+        whatever the mode.  The launch is queued behind read()'s, on the stream read() uses (gather_windows has the rule)."""
+        import torch
+        if layout not in _LAYOUTS:
+            raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
+        if not isinstance(spec, MelSpec) or spec._h is None or spec.ctx is not self.ctx:
+            raise ValueError("read_mel: spec must be an open MelSpec of the set's context")
+        if isinstance(n_frames, bool) or int(n_frames) != n_frames or int(n_frames) < 0:
+            raise ValueError("read_mel: n_frames must be a whole number, not negative")
+        n_frames = int(n_frames)
+        L = spec.window_len(n_frames)
+        audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1)
+        B = int(audio.shape[0])
+        out = torch.empty((B, spec.n_mels, n_frames) if layout == "ct" else (B, n_frames, spec.n_mels), dtype=torch.float32,
+                          device=audio.device)
+        valid = valid.numpy()
+        self.ctx.mel_windows(spec, audio.view(B, L), valid, n_frames, _LAYOUTS[layout], out)
+        return out, torch.from_numpy(np.minimum((valid + spec.hop - 1) // spec.hop, n_frames).astype(np.int64))
 
 
 def open_streams(ctx, streams):

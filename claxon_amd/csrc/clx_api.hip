@@ -12,6 +12,7 @@
 #include "clx_index.hip"
 #include "clx_window.hip"
 #include "clx_mix.hip"                  // (brings clx_resample.hip with it)
+#include "clx_mel.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -265,6 +266,19 @@ struct clx_ctx {
     std::vector<uint32_t> rs_call_fs;
     std::vector<void*> rs_old_dev, rs_old_host;
     hipEvent_t ev_rs_up = nullptr, ev_rs_done = nullptr; bool rs_used = false;
+    // clx_mel_windows: the specs the context owns (each with its tables on the device, written once by clx_mel_create), and the
+    // table of the call's valid_frames with its pinned staging and its two events, by the rules of the window table above
+    std::vector<clx_mel_spec*> mel_specs;
+    uint32_t* d_mel = nullptr; uint32_t* h_mel = nullptr; size_t mel_cap = 0;
+    std::vector<void*> mel_old_dev, mel_old_host;
+    hipEvent_t ev_mel_up = nullptr, ev_mel_done = nullptr; bool mel_used = false;
+};
+
+struct clx_mel_spec {
+    clx_ctx* ctx = nullptr;
+    clx_mel_tables t;
+    void* d_tables = nullptr;          // the basis, the filterbank and the rows' ends, in that order
+    clx_mel_dev dev;
 };
 
 // K2 build by batch size (groups of 64 predictor slots) unless CLX_K2_LATENCY / CLX_K2_THROUGHPUT force one
@@ -436,6 +450,13 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->rs_old_dev.push_back(ctx->d_rs); ctx->rs_old_dev.push_back(ctx->d_rs_coef); ctx->rs_old_host.push_back(ctx->h_rs);
     for (void* p : ctx->rs_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->rs_old_host) if (p) (void)hipHostFree(p);
+    if (ctx->mel_used) (void)hipEventSynchronize(ctx->ev_mel_done);
+    if (ctx->ev_mel_up) (void)hipEventDestroy(ctx->ev_mel_up);
+    if (ctx->ev_mel_done) (void)hipEventDestroy(ctx->ev_mel_done);
+    ctx->mel_old_dev.push_back(ctx->d_mel); ctx->mel_old_host.push_back(ctx->h_mel);
+    for (void* p : ctx->mel_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->mel_old_host) if (p) (void)hipHostFree(p);
+    for (clx_mel_spec* sp : ctx->mel_specs) { if (sp->d_tables) (void)hipFree(sp->d_tables); delete sp; }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1545,6 +1566,76 @@ extern "C" int clx_mix_windows(clx_ctx* ctx, const void* d_src, const uint64_t* 
     if (n_tiles == 0) return CLX_OK;
     return clx_rs_submit(ctx, d_src, src_first, src_t0, src_n, out_t0, valid, src_rate, src_channels, n_windows, out_rate, window_len, out_channels,
                          layout, d_out, stream_, n_tiles);
+}
+
+extern "C" int clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
+                              uint32_t mode, float floor, clx_mel_spec** spec) {
+    if (!ctx) return CLX_API_ERROR;
+    if (!spec) { ctx->last_error = "clx_mel_create: null argument"; return CLX_API_ERROR; }
+    *spec = nullptr;
+    clx_mel_spec* sp = new (std::nothrow) clx_mel_spec();
+    if (!sp) { ctx->last_error = "clx_mel_create: out of memory"; return CLX_API_ERROR; }
+    const std::string why = clx_mel_build(n_fft, hop, window, fbank, n_mels, mode, floor, &sp->t);
+    if (!why.empty()) { delete sp; ctx->last_error = why; return CLX_API_ERROR; }
+    sp->ctx = ctx;
+    const size_t nb = sp->t.basis.size() * 4u, nf = (sp->t.fbank.size() * 4u + 15u) / 16u * 16u, ne = sp->t.ends.size() * 4u;
+    bool ok = hip_ok(ctx, hipSetDevice(ctx->device), "hipSetDevice") &&
+              hip_ok(ctx, hipMalloc(&sp->d_tables, nb + nf + ne), "hipMalloc mel tables");
+    char* d = (char*)sp->d_tables;
+    ok = ok && hip_ok(ctx, hipMemcpy(d, sp->t.basis.data(), nb, hipMemcpyHostToDevice), "H2D mel basis") &&
+         hip_ok(ctx, hipMemcpy(d + nb, sp->t.fbank.data(), sp->t.fbank.size() * 4u, hipMemcpyHostToDevice), "H2D mel filterbank") &&
+         hip_ok(ctx, hipMemcpy(d + nb + nf, sp->t.ends.data(), ne, hipMemcpyHostToDevice), "H2D mel row ends");
+    if (!ok) { if (sp->d_tables) (void)hipFree(sp->d_tables); delete sp; return CLX_API_ERROR; }
+    sp->dev = clx_mel_args(sp->t, (const float*)d, (const float*)(d + nb), (const uint32_t*)(d + nb + nf));
+    std::vector<float>().swap(sp->t.basis);                    // (the device has it; the host copy is not needed again)
+    ctx->mel_specs.push_back(sp);
+    *spec = sp;
+    return CLX_OK;
+}
+
+extern "C" void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec) {
+    if (!ctx || !spec) return;
+    auto it = std::find(ctx->mel_specs.begin(), ctx->mel_specs.end(), spec);
+    if (it == ctx->mel_specs.end()) return;                    // (not this context's, or destroyed already)
+    ctx->mel_specs.erase(it);
+    (void)hipSetDevice(ctx->device);
+    if (ctx->mel_used) (void)hipEventSynchronize(ctx->ev_mel_done);   // (the last launch, hence every launch that may read the tables)
+    if (spec->d_tables) (void)hipFree(spec->d_tables);
+    delete spec;
+}
+
+extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
+                               const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    if (spec && spec->ctx != ctx) { ctx->last_error = "clx_mel_windows: the spec belongs to another context"; return CLX_API_ERROR; }
+    uint32_t n_groups = 0;
+    const char* why = clx_mel_check(spec ? &spec->t : nullptr, d_audio, n_windows, window_len, valid, n_frames, layout, d_out, &n_groups);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (n_groups == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_mel_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_up, hipEventDisableTiming));
+    if (!ctx->ev_mel_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_done, hipEventDisableTiming));
+    if (n_windows > ctx->mel_cap) {                            // a larger table, before anything is queued; the old one is not freed here
+        const size_t want = n_windows + n_windows / 2 + 64;
+        uint32_t* d = nullptr; uint32_t* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc mel table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc mel table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_mel) { ctx->mel_old_dev.push_back(ctx->d_mel); ctx->mel_old_host.push_back(ctx->h_mel); }
+        ctx->d_mel = d; ctx->h_mel = h; ctx->mel_cap = want;
+    } else if (ctx->mel_used) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_mel_up));     // (the upload only: the earlier launch itself is not waited for)
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_mel_done, 0));
+    }
+    clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_up, stream));
+    ctx->mel_used = true;                                      // (from here on the staging and the table are in use)
+    hipLaunchKernelGGL(clx_k_mel, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                       (const uint32_t*)ctx->d_mel, spec->dev, n_groups, window_len, n_frames, layout, (float*)d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_done, stream));
+    return CLX_OK;
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

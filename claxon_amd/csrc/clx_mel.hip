@@ -1,0 +1,282 @@
+// clx_mel.hip -- mel filterbank features of a dense mono batch [B, L] in one launch: framing, a windowed DFT as an fp32 GEMM against a
+// basis table, the power, the band sums and the log, all in clx_k_mel.  claxon_hip.h (clx_mel_create, clx_mel_windows) has the
+// definition; this is how it is computed.
+//
+// A block is one frame group of one window: kF = 32 consecutive frames, all J bins, all bands.  Its work is the GEMM
+// [32 frames x N] . [N x 2J] done in passes of kBins = 256 bins and, inside a pass, in K-slices of kKS = 16 samples:
+//   lane tile   4 bins (cos and sin: 8 basis columns) x 8 frames = 64 accumulators in registers.  Lane q of a wave owns bins
+//               4q .. 4q+3 of the pass, wave w of the block owns frames 8w .. 8w+7 of the group.
+//   basis       the table is stored padded for exactly this: row n holds, for every pass, 256 cos columns then 256 sin columns
+//               (zeros past bin J and in the rows from N up to a multiple of 16), so a K-slice of a pass is 16 runs of 2 KiB that the
+//               block copies with unmasked 16-byte loads into LDS.  A lane reads its 4 cos and 4 sin as two 16-byte LDS reads,
+//               consecutive over the lanes of the wave.
+//   audio       the K-slice of the group's frames is staged unfolded, xs[kk][f] = a[(f0 + f) * H + 16 s + kk] (lanes along kk: 64-byte
+//               runs of the window), so a wave reads its 8 frames as two 16-byte LDS reads at one address.  Overlapping frames are
+//               read from global memory again (N / H times over the K loop: 2.5 at 400 / 160) and not held as one span: the hop
+//               has no upper bound, the span (kF - 1) * H + N has none either, and the audio is 1 / 2J of the operand traffic.
+//   per k       a lane reads 32 bytes of basis and 32 bytes of audio from LDS for 64 fmaf: 1 multiply-add per LDS byte read (the
+//               audio reads are one address per wave).  A basis float comes from the L2 once per 32 frames, not once per frame:
+//               32 multiply-adds per byte of L2 traffic against 0.25 for one bin per lane and one frame per block.
+//   prefetch    the next slice's 8 + 2 global loads are issued into registers before the current slice's 1024 fmaf per lane.
+// After a pass's K loop the lanes square their tile into P[f][bin] in LDS (aliasing the staging area), and the block turns to the
+// band sums: cell (band m, frame f) adds fb[m][j] * P[f][j] over the bins of the pass that lie between the row's first and last
+// non-zero bin, j ascending, one fmaf each.  Cells are dealt to the lanes along the output row of the layout (frames for CT, bands
+// for TC), so the stores are contiguous.  With more than one pass (J > 256: n_fft from 512 up) a cell's sum waits in its own place
+// of the output between passes: the lane that stored it loads it again, nobody else touches it, and the last pass stores the result.
+// A frame at or past valid_frames[k] is stored as +0.0 and costs nothing: its audio is not read, a wave whose 8 frames are all past
+// it skips its fmaf, a block whose 32 are only stores zeros.  No float of the audio outside a live frame is read.
+//
+// LDS: 35 072 bytes, the staging area (16 x 512 basis floats + 16 x 36 audio floats; P, 32 x 260 floats, fits inside): four
+// workgroups share a CU's 160 KiB.
+//
+// clx_mel_build / clx_mel_check / clx_mel_fill are the host side (plain C++, shared with the wave simulator).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+#include "../../include/claxon_hip.h"
+
+// what the kernel needs of a spec (passed by value)
+struct clx_mel_dev {
+    const float* basis;      // [n_pad][n_pass][2][256]: cos then sin of the pass's 256 bins, zero padded
+    const float* fbank;      // [n_mels][J]
+    const uint32_t* ends;    // [n_mels][2]: a row's first non-zero bin and one past its last (equal: an all-zero row)
+    uint32_t n_fft, hop, n_mels, n_bins, n_pass, n_slices, mode;
+    float floor;
+};
+
+// a spec's tables on the host, as clx_mel_build leaves them
+struct clx_mel_tables {
+    uint32_t n_fft = 0, hop = 0, n_mels = 0, n_bins = 0, n_pass = 0, n_slices = 0, mode = 0;
+    float floor = 0.f;
+    std::vector<float> basis, fbank;
+    std::vector<uint32_t> ends;
+};
+
+namespace clx_mel {
+
+constexpr uint32_t kThreads = 256u, kF = 32u, kBins = 256u, kKS = 16u, kRow = 2u * kBins, kXsRow = 36u, kPRow = 260u, kMaxMels = 256u;
+constexpr uint32_t kStage = kKS * kRow + kKS * kXsRow;          // floats of the staging area (P aliases it)
+constexpr uint32_t kLdsBytes = kStage * 4u;                     // 35 072
+static_assert(kF * kPRow <= kStage, "P fits in the staging area");
+static_assert(2u * kLdsBytes <= 160u * 1024u, "two workgroups share a CU's LDS");
+
+// four floats moved as one 16-byte value (a vector type, so that a copy is a load and a store and never a memcpy through a stack slot)
+#if defined(__clang__)
+typedef float f4 __attribute__((ext_vector_type(4)));
+#else
+typedef float f4 __attribute__((vector_size(16)));
+#endif
+
+__device__ __forceinline__ float finish(uint32_t mode, float floor, float m) {
+    if (mode == CLX_MEL_LN) return logf(fmaxf(m, floor));
+    if (mode == CLX_MEL_LOG10) return log10f(fmaxf(m, floor));
+    return m;
+}
+
+// cell c of the block's n_mels x kF cells: lanes run along the layout's output row
+__device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mels, uint32_t* m, uint32_t* f) {
+    if (layout == CLX_WINDOW_CT) { *f = c % kF; *m = c / kF; }
+    else { *m = c % n_mels; *f = c / n_mels; }
+}
+
+}  // namespace clx_mel
+
+// Block b: frame group b % n_groups of window b / n_groups (clx_mel_check gives n_groups).  `audio` is [B, L], vframes[k] =
+// valid_frames[k] <= n_frames, `out` is [B, n_mels, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_mels] (CLX_WINDOW_TC).
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
+                                                            uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
+                                                            float* __restrict__ out) {
+    using namespace clx_mel;
+    __shared__ __attribute__((aligned(16))) float s_stage[kStage];
+    const uint32_t tid = threadIdx.x, k = blockIdx.x / n_groups, f0 = (blockIdx.x - k * n_groups) * kF;
+    const uint32_t vf = vframes[k];
+    const uint32_t nf_out = n_frames - f0 < kF ? n_frames - f0 : kF;                 // the group's frames that exist
+    const uint32_t nf_live = vf > f0 ? (vf - f0 < kF ? vf - f0 : kF) : 0u;           // ... and those that are computed (<= nf_out)
+    const uint32_t cells = S.n_mels * kF;
+    float* const o = out + (uint64_t)k * S.n_mels * n_frames;
+    if (nf_live == 0u) {
+        for (uint32_t c = tid; c < cells; c += kThreads) {
+            uint32_t m, f;
+            cell(c, layout, S.n_mels, &m, &f);
+            if (f < nf_out) o[layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * S.n_mels + m] = 0.f;
+        }
+        return;
+    }
+    const float* const a = audio + (uint64_t)k * L;
+    float* const bs = s_stage;
+    float* const xs = s_stage + kKS * kRow;
+    const uint32_t q = tid & 63u, w = tid >> 6;
+    const bool wave_live = 8u * w < nf_live;
+    // staging duties: basis rows (tid >> 7) + 2 i of the slice, 16 bytes at float 4 * (tid & 127) of the row; audio kk = tid & 15 of
+    // frames (tid >> 4) and (tid >> 4) + 16
+    const uint32_t b_row = tid >> 7, b_col = 4u * (tid & 127u), x_kk = tid & 15u, x_f = tid >> 4;
+    const uint64_t row_stride = (uint64_t)S.n_pass * kRow;
+
+    for (uint32_t p = 0; p < S.n_pass; ++p) {
+        const bool lane_live = wave_live && p * kBins + 4u * q < S.n_bins;
+        float re[4][8], im[4][8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int f = 0; f < 8; ++f) { re[i][f] = 0.f; im[i][f] = 0.f; }
+        const float* const bp = S.basis + (uint64_t)p * kRow + b_col;
+        // round s: slice s goes from global memory into registers, slice s - 1 (in LDS) is computed, then the registers go to LDS
+        for (uint32_t s = 0; s <= S.n_slices; ++s) {
+            f4 pb0, pb1, pb2, pb3, pb4, pb5, pb6, pb7;
+            float px0 = 0.f, px1 = 0.f;
+            if (s < S.n_slices) {
+                const float* const r = bp + ((uint64_t)s * kKS + b_row) * row_stride;
+                pb0 = *reinterpret_cast<const f4*>(r);
+                pb1 = *reinterpret_cast<const f4*>(r + 2u * row_stride);
+                pb2 = *reinterpret_cast<const f4*>(r + 4u * row_stride);
+                pb3 = *reinterpret_cast<const f4*>(r + 6u * row_stride);
+                pb4 = *reinterpret_cast<const f4*>(r + 8u * row_stride);
+                pb5 = *reinterpret_cast<const f4*>(r + 10u * row_stride);
+                pb6 = *reinterpret_cast<const f4*>(r + 12u * row_stride);
+                pb7 = *reinterpret_cast<const f4*>(r + 14u * row_stride);
+                const uint32_t n = s * kKS + x_kk;
+                if (n < S.n_fft) {
+                    if (x_f < nf_live) px0 = a[(uint64_t)(f0 + x_f) * S.hop + n];
+                    if (x_f + 16u < nf_live) px1 = a[(uint64_t)(f0 + x_f + 16u) * S.hop + n];
+                }
+            }
+            if (s > 0u && lane_live) {
+#pragma unroll 4
+                for (uint32_t kk = 0; kk < kKS; ++kk) {
+                    const f4 c4 = *reinterpret_cast<const f4*>(bs + kk * kRow + 4u * q);
+                    const f4 s4 = *reinterpret_cast<const f4*>(bs + kk * kRow + kBins + 4u * q);
+                    const f4 x0 = *reinterpret_cast<const f4*>(xs + kk * kXsRow + 8u * w);
+                    const f4 x1 = *reinterpret_cast<const f4*>(xs + kk * kXsRow + 8u * w + 4u);
+                    const float cv[4] = { c4[0], c4[1], c4[2], c4[3] }, sv[4] = { s4[0], s4[1], s4[2], s4[3] };
+                    const float xv[8] = { x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3] };
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int f = 0; f < 8; ++f) {
+                            re[i][f] = fmaf(xv[f], cv[i], re[i][f]);
+                            im[i][f] = fmaf(xv[f], sv[i], im[i][f]);
+                        }
+                }
+            }
+            __syncthreads();                                   // (slice s - 1, or the pass before's P, has been read)
+            if (s < S.n_slices) {
+                float* const d = bs + b_row * kRow + b_col;
+                *reinterpret_cast<f4*>(d) = pb0;
+                *reinterpret_cast<f4*>(d + 2u * kRow) = pb1;
+                *reinterpret_cast<f4*>(d + 4u * kRow) = pb2;
+                *reinterpret_cast<f4*>(d + 6u * kRow) = pb3;
+                *reinterpret_cast<f4*>(d + 8u * kRow) = pb4;
+                *reinterpret_cast<f4*>(d + 10u * kRow) = pb5;
+                *reinterpret_cast<f4*>(d + 12u * kRow) = pb6;
+                *reinterpret_cast<f4*>(d + 14u * kRow) = pb7;
+                xs[x_kk * kXsRow + x_f] = px0;
+                xs[x_kk * kXsRow + x_f + 16u] = px1;
+            }
+            __syncthreads();                                   // (after the last round: P may take the staging area's place)
+        }
+        float* const P = s_stage;
+        if (lane_live) {
+#pragma unroll
+            for (int f = 0; f < 8; ++f) {
+                f4 v;
+                v[0] = fmaf(re[0][f], re[0][f], im[0][f] * im[0][f]);
+                v[1] = fmaf(re[1][f], re[1][f], im[1][f] * im[1][f]);
+                v[2] = fmaf(re[2][f], re[2][f], im[2][f] * im[2][f]);
+                v[3] = fmaf(re[3][f], re[3][f], im[3][f] * im[3][f]);
+                *reinterpret_cast<f4*>(P + (8u * w + f) * kPRow + 4u * q) = v;
+            }
+        }
+        __syncthreads();
+        const uint32_t j0 = p * kBins, j1 = j0 + kBins;
+        const bool last = p + 1u == S.n_pass;
+        for (uint32_t c = tid; c < cells; c += kThreads) {
+            uint32_t m, f;
+            cell(c, layout, S.n_mels, &m, &f);
+            if (f >= nf_out) continue;
+            float* const at = o + (layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * S.n_mels + m);
+            if (f >= nf_live) { if (last) *at = 0.f; continue; }
+            float acc = p ? *at : 0.f;                         // (this lane's own store of the pass before)
+            const uint32_t e0 = S.ends[2u * m], e1 = S.ends[2u * m + 1u];
+            const uint32_t lo = e0 > j0 ? e0 : j0, hi = e1 < j1 ? e1 : j1;
+            const float* const fb = S.fbank + (uint64_t)m * S.n_bins;
+            const float* const pr = P + f * kPRow;
+            for (uint32_t j = lo; j < hi; ++j) acc = fmaf(fb[j], pr[j - j0], acc);
+            *at = last ? finish(S.mode, S.floor, acc) : acc;
+        }
+    }
+}
+
+// The host side of clx_mel_create: checks the spec's arguments (empty: fine, else the text for clx_last_error) and builds its
+// tables: the basis in double, rounded once, in the padded layout the kernel stages from; a copy of the filterbank; each row's ends.
+inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels, uint32_t mode,
+                                 float floor, clx_mel_tables* t) {
+    if (n_fft < 2u || n_fft > 2048u) return "clx_mel_create: n_fft must be 2..2048";
+    if (hop < 1u) return "clx_mel_create: hop must be at least 1";
+    if (n_mels < 1u || n_mels > clx_mel::kMaxMels) return "clx_mel_create: n_mels must be 1..256";
+    if (mode != CLX_MEL_POWER && mode != CLX_MEL_LN && mode != CLX_MEL_LOG10) return "clx_mel_create: mode must be CLX_MEL_POWER, CLX_MEL_LN or CLX_MEL_LOG10";
+    if (mode != CLX_MEL_POWER && !(floor > 0.f)) return "clx_mel_create: floor must be greater than 0 in a log mode";
+    if (!window || !fbank || !t) return "clx_mel_create: null argument";
+    using namespace clx_mel;
+    const uint32_t N = n_fft, J = N / 2u + 1u;
+    t->n_fft = N; t->hop = hop; t->n_mels = n_mels; t->n_bins = J; t->mode = mode; t->floor = floor;
+    t->n_pass = (J + kBins - 1u) / kBins;
+    t->n_slices = (N + kKS - 1u) / kKS;
+    const size_t row = (size_t)t->n_pass * kRow;
+    t->basis.assign((size_t)t->n_slices * kKS * row, 0.f);
+    const double two_pi = 2.0 * 3.14159265358979323846;
+    for (uint32_t n = 0; n < N; ++n)
+        for (uint32_t j = 0; j < J; ++j) {
+            const double ang = two_pi * (double)(((uint64_t)j * n) % N) / (double)N;     // (in this order: 2 pi k, then / N)
+            float* const at = t->basis.data() + (size_t)n * row + (size_t)(j / kBins) * kRow + j % kBins;
+            at[0] = (float)((double)window[n] * cos(ang));
+            at[kBins] = (float)(-(double)window[n] * sin(ang));
+        }
+    t->fbank.assign(fbank, fbank + (size_t)n_mels * J);
+    t->ends.assign(2u * (size_t)n_mels, 0u);
+    for (uint32_t m = 0; m < n_mels; ++m) {
+        uint32_t lo = J, hi = 0;
+        for (uint32_t j = 0; j < J; ++j)
+            if (fbank[(size_t)m * J + j] != 0.f) { if (lo == J) lo = j; hi = j + 1u; }
+        if (lo == J) lo = hi = 0u;
+        t->ends[2u * m] = lo; t->ends[2u * m + 1u] = hi;
+    }
+    return std::string();
+}
+
+// The host side of clx_mel_windows: checks the arguments (nullptr: fine, else the text for clx_last_error) and gives the launch
+// shape: *n_groups frame groups per window (0: nothing to launch), n_windows * *n_groups blocks of clx_mel::kThreads.
+inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, size_t n_windows, uint32_t window_len, const uint32_t* valid,
+                                 uint32_t n_frames, uint32_t layout, const void* out, uint32_t* n_groups) {
+    *n_groups = 0;
+    if (!t) return "clx_mel_windows: null spec";
+    if (layout != CLX_WINDOW_TC && layout != CLX_WINDOW_CT) return "clx_mel_windows: layout must be CLX_WINDOW_TC or CLX_WINDOW_CT";
+    if (n_windows == 0 || n_frames == 0) return nullptr;
+    if (!audio || !valid || !out) return "clx_mel_windows: null argument";
+    if ((uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len is less than (n_frames - 1) * hop + n_fft";
+    for (size_t k = 0; k < n_windows; ++k)
+        if (valid[k] > window_len) return "clx_mel_windows: valid[k] is larger than window_len";
+    const uint64_t groups = ((uint64_t)n_frames + clx_mel::kF - 1u) / clx_mel::kF;
+    if (groups * (uint64_t)n_windows > 0x7fffffffull) return "clx_mel_windows: too many windows in one call";
+    *n_groups = (uint32_t)groups;
+    return nullptr;
+}
+
+// valid_frames[k] = clamp(ceil(valid[k] / hop), 0, n_frames)
+inline void clx_mel_fill(uint32_t* vframes, const uint32_t* valid, size_t n_windows, uint32_t hop, uint32_t n_frames) {
+    for (size_t k = 0; k < n_windows; ++k) {
+        const uint64_t v = ((uint64_t)valid[k] + hop - 1u) / hop;
+        vframes[k] = v < n_frames ? (uint32_t)v : n_frames;
+    }
+}
+
+inline clx_mel_dev clx_mel_args(const clx_mel_tables& t, const float* basis, const float* fbank, const uint32_t* ends) {
+    clx_mel_dev d;
+    d.basis = basis; d.fbank = fbank; d.ends = ends;
+    d.n_fft = t.n_fft; d.hop = t.hop; d.n_mels = t.n_mels; d.n_bins = t.n_bins; d.n_pass = t.n_pass; d.n_slices = t.n_slices; d.mode = t.mode;
+    d.floor = t.floor;
+    return d;
+}

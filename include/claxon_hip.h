@@ -446,6 +446,48 @@ int  clx_mix_windows(clx_ctx* ctx, const void* d_src, const uint64_t* src_first,
                      const uint64_t* out_t0, const uint32_t* valid, const uint32_t* src_rate, const uint8_t* src_channels,
                      size_t n_windows, uint32_t out_rate, uint32_t window_len, uint32_t out_channels, uint32_t layout, void* d_out,
                      void* stream);
+/* Mel filterbank features of a dense mono batch, in one launch (clx_k_mel).
+ *
+ * A spec is (n_fft N, hop H, a float32 window w[N], a float32 filterbank fb[n_mels][J], mode, floor) with N in 2..2048,
+ * J = floor(N/2) + 1, H any whole number from 1 up (H > N is allowed) and n_mels in 1..256.  For a batch a[B][L] (float32) with
+ * valid[k] <= L:
+ *   frames     frame t of window k is x[n] = a[k][t*H + n], n = 0..N-1: no centring, no reflection.  The caller guarantees
+ *              (n_frames-1)*H + N <= L (checked), and that the samples at or past valid[k] are zero (not checked and not
+ *              re-masked: StreamSet.read and the window readers above write them as zero).
+ *   basis      c[j][n] = fl32(w[n] * cos(2 pi ((j n) mod N) / N)), s[j][n] = fl32(-w[n] * sin(2 pi ((j n) mod N) / N)): built on
+ *              the host in double, rounded once, once per spec, kept on the context.
+ *   power      re_j = sum_n x[n] c[j][n], im_j = sum_n x[n] s[j][n], P_j = re_j^2 + im_j^2, M_m = sum_j fb[m][j] P_j, all in
+ *              float32.  The order of the sums is the kernel's and it uses fused multiply-adds; for ANY order
+ *              |M_m - exact| <= dM_m with, u = 2^-24 and g(k) = k u / (1 - k u): dre_j = g(N+2) sum_n |x[n] w[n] cos|, dim_j
+ *              likewise, E_j = 2|re_j| dre_j + dre_j^2 + 2|im_j| dim_j + dim_j^2, dP_j = E_j + g(3)(P_j + E_j),
+ *              dM_m = sum_j fb[m][j] dP_j + g(J_m + 1) sum_j fb[m][j](P_j + dP_j), J_m the row's bin count.
+ *   rows       a filterbank row is summed only from its first to its last non-zero bin (the library finds them in the dense
+ *              table); an all-zero row gives 0.
+ *   mode       CLX_MEL_POWER: M_m.  CLX_MEL_LN: logf(max(M_m, floor)).  CLX_MEL_LOG10: log10f(max(M_m, floor)).  The modes
+ *              differ in that last step only: M_m is bitwise the same in all three (and in both layouts).
+ *   validity   valid_frames[k] = clamp(ceil(valid[k] / H), 0, n_frames).  A frame at or past it is written as +0.0 in every
+ *              mode and its DFT is not computed.  The call writes all of d_out.
+ *   layout     CLX_WINDOW_CT: out[k][m][t], a [B, n_mels, n_frames] tensor.  CLX_WINDOW_TC: out[k][t][m], [B, n_frames, n_mels]:
+ *              the bands take the channels' place.
+ * No float of d_audio outside [0, B*L) is read (none outside a frame below valid_frames[k], in fact).
+ *
+ * clx_mel_create checks the ranges, builds the basis, uploads it with the filterbank and the rows' ends (it synchronises) and
+ * returns a handle owned by the context: clx_destroy frees what clx_mel_destroy did not.  CLX_API_ERROR (clx_last_error says
+ * why) for a null argument, n_fft, hop or n_mels out of range, an unknown mode, and a floor that is not > 0 in a log mode (in
+ * CLX_MEL_POWER the floor is not used).  clx_mel_destroy waits for the launches that use the handle. */
+enum { CLX_MEL_POWER = 0, CLX_MEL_LN = 1, CLX_MEL_LOG10 = 2 };
+typedef struct clx_mel_spec clx_mel_spec;
+int  clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
+                    uint32_t mode, float floor, clx_mel_spec** spec);
+void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
+/* The features of d_audio [n_windows][window_len] (device, float32) into d_out (device, float32), asynchronously on `stream`
+ * (NULL: the context's).  valid is a host array; it is staged like the window table of clx_gather_windows: pinned staging, a
+ * table that has to grow is replaced before anything is queued, one event behind the upload and one behind the launch, so the
+ * call returns without waiting for the device and valid may be reused at once.  CLX_API_ERROR for a null argument, a spec of
+ * another context, window_len < (n_frames-1)*hop + n_fft, a valid[k] > window_len and an unknown layout.  n_windows == 0 or
+ * n_frames == 0 succeeds and launches nothing. */
+int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
+                     const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
