@@ -99,19 +99,23 @@ def span(m0, m1, T, fs, R):
     return max(0, m0 * o // n - W + 1), min(T, m1 * o // n + W + 1)
 
 
-def reference(x, fs, R, m):
+def reference(x, fs, R, m, t0=0):
     """y64[m, c] and the tolerance's sum of |h_k x_k| for outputs `m` (an int array) of x [T, C] (float32, taken as float64) resampled
-    from fs to R: every one of the 2W taps evaluated from the formula, x = 0 outside 0 <= s < T."""
+    from fs to R: every one of the 2W taps evaluated from the formula, x = 0 outside 0 <= s < T.  With t0, row 0 of x is stream
+    sample t0 (x = 0 outside t0 <= s < t0 + T): a piece of a stream far from its start, without the zeros in front of it.  The
+    positions are whole numbers throughout (int64: m * o is checked to fit), only the tap's distance s - m o / n becomes a double."""
     o, n, W = pair(fs, R)
     base = min(o, n) * 0.99
     x = np.asarray(x, dtype=np.float64)
     T = x.shape[0]
     m = np.asarray(m, dtype=np.int64)
+    assert m.size == 0 or (int(np.abs(m).max()) + 1) * o + 2 * W < 1 << 63, "m * o does not fit int64"
     fc = m * o // n
     s = fc[:, None] - W + 1 + np.arange(2 * W)[None, :]                          # [M, 2W]
     d = (s - fc[:, None]).astype(np.float64) - ((m * o) % n).astype(np.float64)[:, None] / n      # s - m o / n: the whole part in integers
     t = d * base / o
     h = np.where(np.abs(t) < 6.0, np.sinc(t) * np.cos(np.pi * t / 12.0) ** 2 * base / o, 0.0)
+    s = s - int(t0)                                                              # (from here on: rows of x)
     inside = (s >= 0) & (s < T)
     xs = np.where(inside[:, :, None], x[np.clip(s, 0, max(T - 1, 0))], 0.0)      # [M, 2W, C]
     terms = h[:, :, None] * xs
@@ -124,9 +128,10 @@ def bound(fs, R):
     return N * U / (1.0 - N * U)
 
 
-def assert_close(got, x, fs, R, m, what=""):
-    """got [M, C] (float32) against the reference for outputs m: |y - y64| <= gamma * sum |h_k x_k|, exactly 0 where no tap is."""
-    y, mag = reference(x, fs, R, m)
+def assert_close(got, x, fs, R, m, what="", t0=0):
+    """got [M, C] (float32) against the reference for outputs m: |y - y64| <= gamma * sum |h_k x_k|, exactly 0 where no tap is.
+    Returns the worst |error| / bound."""
+    y, mag = reference(x, fs, R, m, t0)
     got = np.asarray(got, dtype=np.float64)
     assert got.shape == y.shape, (got.shape, y.shape, what)
     err, tol = np.abs(got - y), bound(fs, R) * mag

@@ -62,20 +62,21 @@ def _stream(rng, n, ch, bs, bps, rate, last=0):
 
 
 class Case:
-    """A stream, its whole decode by load() (computed once, kept on the host as the reference's input) and its single-stream set."""
+    """A stream, its whole decode by load() (computed once, kept on the host as the reference's input) and its single-stream set;
+    `at` is the rate its windows are read at."""
 
-    def __init__(self, ctx, data, bounds):
-        self.data, self.bounds = data, bounds
+    def __init__(self, ctx, data, bounds, at=R):
+        self.data, self.bounds, self.at, self.worst = data, bounds, at, 0.0
         ref, self.rate = cx.load(ctx, data)
         self.x = ref.cpu().numpy()
         self.T, self.C = self.x.shape
         assert self.T == bounds[-1]
-        self.T_R = self.T if self.rate == R else sr.length_at(self.T, self.rate, R)
+        self.T_R = self.T if self.rate == at else sr.length_at(self.T, self.rate, at)
         self.set = cx.open_streams(ctx, [data])
         assert self.set.problems == [None] and self.set.sample_rates == [self.rate] and int(self.set.lengths[0]) == self.T
 
     def span(self, st, valid):
-        return (st, st + valid) if self.rate == R else sr.span(st, st + valid - 1, self.T, self.rate, R)
+        return (st, st + valid) if self.rate == self.at else sr.span(st, st + valid - 1, self.T, self.rate, self.at)
 
     def frames_for(self, st, L):
         """The frames that cover the source span of outputs st .. st + L - 1, counted from the frame boundaries."""
@@ -86,13 +87,13 @@ class Case:
         return sum(1 for a, b in zip(self.bounds[:-1], self.bounds[1:]) if a < hi and b > lo)
 
     def check(self, got, st, L, what):
-        """got [L, C] (a numpy array): window st of this stream at R."""
+        """got [L, C] (a numpy array): window st of this stream at `at`.  Returns valid; .worst keeps the worst |error| / bound seen."""
         valid = min(max(self.T_R - st, 0), L)
         assert np.all(got[valid:].view(np.uint32) == 0), (what, "the window's tail is not zeros")
-        if self.rate == R:
+        if self.rate == self.at:
             assert np.array_equal(got[:valid], self.x[st:st + valid]), what
         elif valid:
-            sr.assert_close(got[:valid], self.x, self.rate, R, np.arange(st, st + valid), what)
+            self.worst = max(self.worst, sr.assert_close(got[:valid], self.x, self.rate, self.at, np.arange(st, st + valid), what))
         return valid
 
 
@@ -107,7 +108,7 @@ def cases(ctx):
 
 def _starts(c, L):
     """0, round every frame boundary mapped to the output rate, across the stream's end, at it and behind it."""
-    o, n, _ = cx.resample_pair(c.rate, R)
+    o, n, _ = cx.resample_pair(c.rate, c.at)
     st = {0, c.T_R - L // 2, c.T_R - 1, c.T_R, c.T_R + 5}
     for b in c.bounds:
         st |= {b * n // o + d for d in (-1, 0, 1)}

@@ -13,8 +13,9 @@ import simlib_mel as sm
 NAN_FILL = 0x7fc0dead            # a quiet NaN with a payload: what the output holds before the call
 GUARD = 0xffc0beef               # the word behind the output
 SR = 16000
-# (n_fft, hop, n_mels): the last but one has hop > n_fft; the last has J = 301 bins, two passes of the kernel's 256
-SHAPES = ((400, 160, 80), (64, 24, 13), (50, 7, 5), (16, 40, 3), (600, 200, 40))
+# (n_fft, hop, n_mels): (16, 40, 3) has hop > n_fft; (600, 200, 40) has J = 301 bins, two passes of the kernel's 256, the second
+# partial; (512, 128, 64) has J = 257, a second pass of one bin; (510, 170, 64) has J = 256, one pass that is exactly full
+SHAPES = ((400, 160, 80), (64, 24, 13), (50, 7, 5), (16, 40, 3), (600, 200, 40), (512, 128, 64), (510, 170, 64))
 GROUP = 32                       # clx_mel::kF, a block's frame group
 FRAMES = (1, 37, GROUP + 1)
 LAYOUTS = (sm.CT, sm.TC)

@@ -3,7 +3,8 @@ wave simulator, against the resampler's definition evaluated in float64 with num
 source samples, without the library's table).  Per output |y - y64| <= gamma * sum_k |h_k x_k| with gamma = N u / (1 - N u),
 u = 2^-24, N = 2W + 2 -- the bound of an N-term float32 dot product in any order, one term more for the table's single rounding and
 one for libm's double -- and an output without a tap inside the stream is exactly 0.  The source is 700 random samples per channel;
-every window's span sits in the source between NaNs, so a tap taken from outside the span shows in the result."""
+every window's span sits in the source between NaNs, so a tap taken from outside the span shows in the result.  One test moves
+the windows to where out_t0 + L is just below 2^43, the largest the call accepts (far_windows, shared with the GPU tests)."""
 import numpy as np
 import pytest
 
@@ -172,6 +173,46 @@ def test_loads_stay_inside_the_span(C, layout):
                     sr.assert_close(got[:w.valid], x, fs, R, np.arange(st, st + w.valid), (fs, R, C, layout, st, at_end))
                 else:
                     assert w.hi == w.lo
+
+
+FAR = 1 << 43                    # clx_rs::kMaxOut: out_t0 + L stays below it
+
+
+def far_windows(seed, C, L, fs=44100, R=16000):
+    """Three windows whose last output is one of the last below 2^43, at three phases (out_t0 mod n), of a stream taken as endless.
+    Only the positions are large: a window's source is its span by the formula, noise, and nothing else.  Returns (the source buffer
+    with the spans between NaNs from an odd float on, the per-window arguments of resample_windows in its order, the spans)."""
+    o, n, _ = sr.pair(fs, R)
+    rng = np.random.default_rng(seed)
+    out_t0 = [FAR - L - back for back in (1, 2, 79)]
+    assert len({m0 % n for m0 in out_t0}) == 3 and min(out_t0) > 1 << 42
+    spans = [sr.span(m0, m0 + L - 1, 1 << 62, fs, R) for m0 in out_t0]
+    xs = [rng.uniform(-1.0, 1.0, size=(hi - lo, C)).astype(np.float32) for lo, hi in spans]
+    parts, first = [np.full(1, np.nan, dtype=np.float32)], []
+    for x in xs:
+        first.append(sum(p.size for p in parts))
+        parts += [x.reshape(-1), np.full(3, np.nan, dtype=np.float32)]
+    assert any(f % 2 for f in first)
+    args = (first, [lo for lo, _ in spans], [hi - lo for lo, hi in spans], out_t0, [L] * 3, [fs] * 3)
+    return np.ascontiguousarray(np.concatenate(parts)), args, xs
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_windows_that_end_just_below_two_to_the_43(layout):
+    """The block's one 64-bit product and quotient, m0 * o / n, at the largest m0 the call accepts (m0 * o is about 2^51.8), in the
+    window's first tile and in its second; the reference takes the same positions as int64."""
+    C, L, fs, R = 2, TILE + 6, 44100, 16000
+    src, args, xs = far_windows(43, C, L, fs, R)
+    n = 3 * L * C
+    buf = np.full(n + 1, NAN_FILL, dtype=np.uint32)
+    buf[n] = GUARD
+    sr.resample_windows(src, *args, R, L, C, layout, buf)
+    assert buf[n] == GUARD, "the word behind the output was written"
+    out = buf[:n].view(np.float32)
+    got = out.reshape(3, C, L).transpose(0, 2, 1) if layout == sr.CT else out.reshape(3, L, C)
+    for k, x in enumerate(xs):
+        worst = sr.assert_close(got[k], x, fs, R, args[3][k] + np.arange(L, dtype=np.int64), (layout, k), t0=args[1][k])
+        print("out_t0 2^43 - %d, layout %d: worst |error| / bound %.3f" % (FAR - args[3][k], layout, worst))
 
 
 def test_refused_arguments_and_empty_calls():
