@@ -21,14 +21,12 @@ import claxon_amd as cx
 import simlib_mel as sml
 import simlib_mix as smx
 import simlib_resample as sr
+from gpu_guarded import DEV, NAN_FILL, device_out as _device_out, written as _written
 from test_gpu_resample import SHAPES as STREAMS, Case, _starts, _stream
 from test_mel_sim import _batch, _check_power
 from test_resample_sim import far_windows
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-NAN_FILL = 0x7fc0dead            # a quiet NaN with a payload: what the output and its guards hold before the call
-GUARD = 64                       # words before the output and behind it
 SR = 16000
 FLOOR = 1e-10
 TC, CT = cx.WINDOW_TC, cx.WINDOW_CT
@@ -40,23 +38,6 @@ def ctx():
 
 
 # ---- the output buffer and the comparison -------------------------------------------------------------------------------------------
-
-def _device_out(n):
-    """(the whole buffer, the n floats of it that the call may write), every word NAN_FILL."""
-    flat = torch.from_numpy(np.full(n + 2 * GUARD, NAN_FILL, dtype=np.uint32).view(np.float32)).to(DEV)
-    return flat, flat[GUARD:GUARD + n]
-
-
-def _written(flat, n, what):
-    """The n output words on the host, after the checks that the guards are untouched and that every output word was written."""
-    h = flat.cpu().numpy().view(np.uint32)
-    assert np.all(h[:GUARD] == NAN_FILL), (what, "a guard word before the output was written")
-    assert np.all(h[GUARD + n:] == NAN_FILL), (what, "a guard word behind the output was written")
-    body = h[GUARD:GUARD + n]
-    left = int(np.count_nonzero(body == NAN_FILL))
-    assert left == 0, (what, "%d of %d output words still hold the fill pattern" % (left, n))
-    return body
-
 
 def _same_words(got, want, axes, what):
     """got and want ([B, x, y] float32) as 32-bit words; returns the cells compared."""

@@ -9,80 +9,39 @@ import md5_cases as mc
 import simlib_md5 as sm
 
 
-def _flat(streams, fmt, bps_list, rng=None, gap=0):
-    """Streams of samples packed one after another (with `gap` samples between) in one source buffer: (buffer, first, counts)."""
-    parts, first, counts, at = [], [], [], 0
-    for vals, bps in zip(streams, bps_list):
-        if gap:
-            parts.append(mc.encode(np.zeros(gap, dtype=np.int64), fmt, bps))
-            at += gap
-        parts.append(mc.encode(vals, fmt, bps))
-        first.append(at)
-        counts.append(len(vals))
-        at += len(vals)
-    buf = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
-    return buf, np.array(first, dtype=np.uint64), np.array(counts, dtype=np.uint64)
-
-
-def _check(streams, fmt, bps_list, gap=0):
-    buf, first, counts = _flat(streams, fmt, bps_list, gap=gap)
-    got = sm.md5_streams(buf, fmt, first, counts, bps_list)
-    for k, (vals, bps) in enumerate(zip(streams, bps_list)):
-        assert bytes(got[k]) == mc.ref_md5(vals, bps), (k, len(vals), bps, fmt)
+def run_sim(buf, fmt, first, counts, bps, byte_offset=0):
+    """The runner of md5_cases' checks: the source bytes as they are, or byte_offset bytes behind a 16-byte boundary of a larger array."""
+    if byte_offset:
+        big = np.zeros(buf.size + 64, dtype=np.uint8)
+        base = (-big.ctypes.data) % 16 + byte_offset
+        big[base:base + buf.size] = buf
+        buf = big[base:base + buf.size]
+        assert buf.ctypes.data % 16 == byte_offset
+    return sm.md5_streams(buf, fmt, first, counts, bps)
 
 
 def test_every_message_length_to_300_bytes():
     """0..300 message bytes at each width: the padding's edges 55/56/63/64/119/120 and every partial group."""
-    rng = np.random.default_rng(1)
-    for w in (1, 2, 3, 4):
-        bps = 8 * w
-        streams = [mc.random_samples(rng, nb // w, bps) for nb in range(0, 301) if nb % w == 0]
-        _check(streams, w, [bps] * len(streams))
+    assert mc.check_every_message_length(run_sim) == (4, 301 + 151 + 101 + 76)
 
 
 def test_every_format_with_every_width_it_holds():
-    rng = np.random.default_rng(2)
-    for fmt in mc.FORMATS:
-        for bps in mc.valid_bps(fmt):
-            lens = [0, 1, 15, 16, 17, 63, 64, 65, 191, 192, 193, 1000, int(rng.integers(2000, 5000))]
-            _check([mc.random_samples(rng, n, bps) for n in lens], fmt, [bps] * len(lens))
+    assert mc.check_every_format_and_width(run_sim) == (3 + 6 + 9 + 12 + 9, 39 * 13)
 
 
 def test_f32_extremes_scale_back_exactly():
     """The floats of -2^(bps-1) and 2^(bps-1) - 1 (the full range), 0 and +-1 for every width F32 holds."""
-    for bps in (1, 2, 8, 12, 16, 20, 23, 24):
-        lo, hi = -(1 << (bps - 1)), (1 << (bps - 1)) - 1
-        vals = np.array([lo, hi, 0, 1, -1, lo + 1, hi - 1] * 37, dtype=np.int64)
-        vals = np.clip(vals, lo, hi)
-        _check([vals, vals[:5], vals[:64]], cx.SAMPLE_F32, [bps] * 3)
+    assert mc.check_f32_extremes(run_sim) == (8, 24)
 
 
 def test_any_alignment_of_a_stream_start():
     """Streams at odd sample indices, and the whole buffer at byte offsets 1..15 from a 16-byte boundary."""
-    rng = np.random.default_rng(3)
-    for fmt in mc.FORMATS:
-        bps = 8 * min(mc.sample_size(fmt), 3)
-        streams = [mc.random_samples(rng, n, bps) for n in (100, 257, 31, 640, 3)]
-        _check(streams, fmt, [bps] * len(streams), gap=1)
-        buf, first, counts = _flat(streams, fmt, [bps] * len(streams), gap=3)
-        for off in range(1, 16):
-            big = np.zeros(buf.size + 64, dtype=np.uint8)
-            base = (-big.ctypes.data) % 16 + off
-            big[base:base + buf.size] = buf
-            got = sm.md5_streams(big[base:base + buf.size], fmt, first, counts, [bps] * len(streams))
-            for k, vals in enumerate(streams):
-                assert bytes(got[k]) == mc.ref_md5(vals, bps), (fmt, off, k)
+    assert mc.check_any_alignment_of_a_stream_start(run_sim) == (5 * 16, 5 * 16 * 5)
 
 
 def test_many_streams_of_very_different_lengths_in_one_call():
     """150 streams, empty ones among them, of lengths from 0 to 40000 samples and widths 1..4 (every width class, one launch each)."""
-    rng = np.random.default_rng(4)
-    lens = [0, 0, 1, 40000, 7] + [int(x) for x in rng.integers(0, 3000, size=145)]
-    bps = [int(b) for b in rng.choice([4, 8, 12, 16, 20, 24, 28, 32], size=len(lens))]
-    streams = [mc.random_samples(rng, n, b) for n, b in zip(lens, bps)]
-    _check(streams, 4, bps)
-    bps24 = [min(b, 24) for b in bps]
-    _check([np.clip(s, -(1 << (b - 1)), (1 << (b - 1)) - 1) for s, b in zip(streams, bps24)], cx.SAMPLE_F32, bps24)
+    assert mc.check_many_streams_of_mixed_width(run_sim) == (2, 300)
 
 
 def test_loads_stay_inside_the_stream():

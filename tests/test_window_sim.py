@@ -1,123 +1,67 @@
 """The window gather (clx_window.hip: clx_window_check and clx_k_window) under the wave simulator, against numpy slicing of the same
 source, bit for bit (as uint32): window lengths round the vector, wave and tile sizes, 1..8 channels, both layouts, every alignment
 of a window's start, valid counts 0 / 1 / L-1 / L, more windows than a workgroup has lanes, overlapping and descending windows, an
-output the test fills with NaN patterns (every element is overwritten, the float behind the output is not), loads that stay inside
+output the test fills with NaN patterns (every element is overwritten, the words round the output are not), loads that stay inside
 [src_first, src_first + valid * C) next to an inaccessible page, and the refused arguments."""
 import numpy as np
 import pytest
 
 import claxon_amd as cx
 import simlib_window as sw
+import window_cases as wc
 
-NAN_FILL = 0x7fc0dead            # a quiet NaN with a payload: what the output holds before the call
-GUARD = 0xffc0beef               # the word behind the output
-LENGTHS = (1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1000)
-CHANNELS = (1, 2, 3, 8)
+NAN_FILL = wc.NAN_FILL
+GUARD = 0xffc0beef               # the words round the output
 LAYOUTS = (sw.TC, sw.CT)
+assert LAYOUTS == wc.LAYOUTS
+_aligned = lambda n_words: wc.aligned(n_words)[1]
+_expect = wc.expect
 
 
-def _aligned(n_words, offset_words=0, align=64):
-    """A uint32 array of n_words whose first word sits offset_words words behind an `align`-byte boundary."""
-    raw = np.zeros(n_words + align // 4 + offset_words + 4, dtype=np.uint32)
-    at = ((-raw.ctypes.data) % align) // 4 + offset_words
-    return raw[at:at + n_words]
-
-
-def _source(rng, n_words):
-    src = _aligned(n_words)
-    src[:] = rng.integers(0, 1 << 32, size=n_words, dtype=np.uint64).astype(np.uint32)     # (any bit pattern: NaNs and denormals too)
-    return src
-
-
-def _expect(src, src_first, valid, L, C, layout):
-    out = np.zeros((len(src_first), L, C), dtype=np.uint32)
-    for k, (s, v) in enumerate(zip(src_first, valid)):
-        out[k, :v] = src[int(s):int(s) + int(v) * C].reshape(int(v), C)
-    return np.ascontiguousarray(out.transpose(0, 2, 1)) if layout == sw.CT else out
-
-
-def _run(src, src_first, valid, L, C, layout, out_offset_words=0):
-    """The call on an output pre-filled with NaN patterns and followed by a guard word; returns the output, flat."""
+def run_sim(src, src_first, valid, L, C, layout, out_offset_words=0):
+    """The runner of window_cases' checks: the call on an output pre-filled with NaN patterns inside an array of guard words."""
     n = len(src_first) * L * C
-    buf = _aligned(n + 1, out_offset_words)
+    raw, buf = wc.aligned(n, out_offset_words, fill=GUARD)
+    assert buf.ctypes.data % 16 == 4 * out_offset_words
     buf[:] = NAN_FILL
-    buf[n] = GUARD
     sw.gather_windows(src, src_first, valid, L, C, layout, buf)
-    assert buf[n] == GUARD, "the word behind the output was written"
-    return buf[:n]
-
-
-def _check(src, src_first, valid, L, C, layout, out_offset_words=0):
-    got = _run(src, src_first, valid, L, C, layout, out_offset_words)
-    want = _expect(src, src_first, valid, L, C, layout).reshape(-1)
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, (L, C, layout, out_offset_words, "first difference at word %d: %#x, expected %#x" % (bad[0], got[bad[0]], want[bad[0]]))
+    at = (buf.ctypes.data - raw.ctypes.data) // 4 if n else 0
+    return buf.copy(), bool(np.all(raw[:at] == GUARD) and np.all(raw[at + n:] == GUARD))
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
-@pytest.mark.parametrize("C", CHANNELS)
+@pytest.mark.parametrize("C", wc.CHANNELS)
 def test_lengths_alignments_and_valid_counts(C, layout):
     """Every L, with one call of 32 windows each: src_first mod 8 over 0..7 times valid in {0, 1, L-1, L}."""
-    rng = np.random.default_rng(100 * C + layout)
-    for L in LENGTHS:
-        src = _source(rng, 32 * (L * C + 16) + 64)
-        first, valid, at = [], [], 0
-        for a in range(8):
-            for v in (0, 1, L - 1, L):
-                at = (at + 7) // 8 * 8 + a
-                first.append(at)
-                valid.append(v)
-                at += L * C
-        assert all(f % 8 == k // 4 for k, f in enumerate(first))
-        _check(src, first, valid, L, C, layout)
+    assert wc.check_lengths_alignments_and_valid_counts(run_sim, C, layout) == (11, 32 * C * sum(wc.LENGTHS))
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_output_on_a_4_byte_boundary_only(layout):
     """An output 1..3 words off the 16-byte grid: the first window has a ragged head too."""
-    rng = np.random.default_rng(7)
-    for off in (1, 2, 3):
-        for L, C in ((5, 3), (64, 2), (257, 1), (256, 8)):
-            src = _source(rng, 4 * L * C + 16)
-            _check(src, [3, L * C + 2, 1], [L, L - 1, L], L, C, layout, out_offset_words=off)
+    assert wc.check_output_on_a_4_byte_boundary_only(run_sim, layout)[0] == 15
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
-@pytest.mark.parametrize("B", (0, 1, 70))
+@pytest.mark.parametrize("B", wc.BATCHES)
 def test_batch_sizes(B, layout):
     """No window, one, and 70 (more than one workgroup has lanes... and than a wave) with mixed valid counts in one call."""
-    rng = np.random.default_rng(B)
-    for L, C in ((257, 2), (256, 3), (1000, 2)):
-        src = _source(rng, 8192)
-        first = rng.integers(0, 8192 - L * C, size=B)
-        valid = rng.integers(0, L + 1, size=B)
-        if B:
-            valid[0] = L
-            valid[-1] = 0
-        _check(src, first, valid, L, C, layout)
+    assert wc.check_batch_sizes(run_sim, B, layout) == (3, B * (257 * 2 + 256 * 3 + 1000 * 2))
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_a_window_of_several_tiles(layout):
     """Windows longer than one tile of 4096 floats / samples: the tiles of a window meet without a gap, the last one is partial."""
-    rng = np.random.default_rng(11)
-    for L, C in ((4096 + 5, 2), (2 * 4096, 1), (4099, 3)):
-        src = _source(rng, 2 * L * C + 64)
-        _check(src, [5, L * C - 7, 0], [L, L - 3, 4097], L, C, layout)
+    assert wc.check_a_window_of_several_tiles(run_sim, layout)[0] == 4
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_overlapping_and_descending_windows(layout):
-    rng = np.random.default_rng(13)
-    L, C = 65, 2
-    src = _source(rng, 2048)
-    first = [1000, 1001, 1002, 1064, 900, 500, 499, 2, 0, 0]         # (overlapping in src, then descending, then the same twice)
-    valid = [L, L, L - 1, L, 1, L, L, 0, L, L]
-    _check(src, first, valid, L, C, layout)
+    assert wc.check_overlapping_and_descending_windows(run_sim, layout) == (1, 10 * 65 * 2)
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
-@pytest.mark.parametrize("C", CHANNELS)
+@pytest.mark.parametrize("C", (1, 2, 3, 8))
 def test_loads_stay_inside_the_valid_region(C, layout):
     """The valid region ends on the last float before an inaccessible page, for every tail 1..9 samples past a whole number of
     vectors, waves and none at all; and it begins on the first float behind an inaccessible page.  A stray load would fault."""
