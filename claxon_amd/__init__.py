@@ -33,6 +33,7 @@ OUT_F32 = 65536             # the same with channel-interleaved float32 normaliz
 SAMPLE_F32 = 0x104          # sample format of interleave / decode_frames_stream: the floats of OUT_F32 (next to sample_bytes 1..4)
 WINDOW_TC, WINDOW_CT = 0, 1   # clx_gather_windows layouts: [B, L, C] and [B, C, L]
 MEL_POWER, MEL_LN, MEL_LOG10 = 0, 1, 2   # clx_mel_create modes
+MEL_PAD_REFLECT, MEL_PAD_ZERO = 0, 1     # clx_mel_opts.pad
 SUBMIT_DEPTH = 24           # CLX_SUBMIT_DEPTH: the most submissions a Batch keeps in flight (Batch.submit_depth: this batch's)
 
 
@@ -100,7 +101,7 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
-    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_destroy", "clx_mel_windows",
+    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_destroy", "clx_mel_windows",
 ]
 
 
@@ -183,6 +184,7 @@ def lib():
     L.clx_resample_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_mix_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_mel_create.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(vp)]
+    L.clx_mel_create_ex.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, vp, C.POINTER(vp)]
     L.clx_mel_destroy.argtypes = [vp, vp]
     L.clx_mel_destroy.restype = None
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
@@ -711,7 +713,8 @@ class Context:
     def mel_windows(self, spec, audio, valid, n_frames, layout, out, stream=None):
         """clx_mel_windows: the features of `spec` (a MelSpec of this context) for the dense mono batch `audio` [B, L] (float32, the
         samples from valid[k] on zero), n_frames frames per window, written to `out` as [B, n_frames, n_mels] (WINDOW_TC) or
-        [B, n_mels, n_frames] (WINDOW_CT); a frame from ceil(valid[k] / hop) on is zeros.  `audio` and `out` are CUDA float32 tensors
+        [B, n_mels, n_frames] (WINDOW_CT); a frame from spec.valid_frames(valid[k], n_frames) on is zeros (the scaled silence value
+        for a spec with top).  A centred spec takes the [B, L] batch as the crops its frames are centred on.  `audio` and `out` are CUDA float32 tensors
         (B and L are the tensor's) or `audio` is a (pointer, B, L) triple and `out` a pointer.  Asynchronous on `stream` as
         gather_windows is."""
         if getattr(spec, "_h", None) is None or spec.ctx is not self:
@@ -1241,6 +1244,12 @@ def verify(ctx, streams):
 # ---- mel features ---------------------------------------------------------------------------------------------------------------------
 
 _MEL_MODES = {"power": MEL_POWER, "ln": MEL_LN, "log10": MEL_LOG10}
+_MEL_PADS = {"reflect": MEL_PAD_REFLECT, "zeros": MEL_PAD_ZERO}
+
+
+class _MelOpts(C.Structure):             # clx_mel_opts
+    _fields_ = [("center", C.c_uint32), ("pad", C.c_uint32), ("range", C.c_uint32), ("range_width", C.c_float), ("shift", C.c_float),
+                ("scale", C.c_float)]
 
 
 def _hz_to_mel(f, scale):
@@ -1303,10 +1312,16 @@ class MelSpec:
     step -- mode "power" (the band sums), "ln" or "log10" (the logarithm of max(band sum, floor)).  Both tables are built with
     numpy in double and rounded once to float32.  The spec owns the library's handle (the DFT basis is built and uploaded here,
     once) until close().  ctx=None builds the tables only.  ValueError for arguments out of range and for a filterbank with an empty
-    band."""
+    band.
+
+    center=True frames as torch.stft(center=True) does: frame t is centred on sample t * hop of the window continued by n_fft // 2
+    samples on both sides, by reflection about the window's own ends (pad_mode="reflect") or by zeros ("zeros").  top=D (log modes)
+    turns range scaling on: every cell is clamped to the window's maximum minus D, then (y + shift) * scale; a frame past the
+    window's valid samples then holds the scaled silence value and not zeros.  (clx_mel_create_ex, claxon_hip.h, has both in full.)
+    Without them the spec is what it always was."""
 
     def __init__(self, ctx, sample_rate, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, mode="ln",
-                 floor=1e-10):
+                 floor=1e-10, center=False, pad_mode="reflect", top=None, shift=0.0, scale=1.0):
         self.ctx, self._h = ctx, None
         for name, v in (("sample_rate", sample_rate), ("n_fft", n_fft), ("hop", hop), ("n_mels", n_mels)):
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v:
@@ -1319,17 +1334,58 @@ class MelSpec:
         self.mode, self.floor = mode, float(np.float32(floor))
         if mode != "power" and not self.floor > 0:
             raise ValueError("MelSpec: floor must be greater than 0 in mode %r" % mode)
+        if not isinstance(center, (bool, np.bool_)):
+            raise ValueError("MelSpec: center must be True or False, not %r" % (center,))
+        if pad_mode not in _MEL_PADS:
+            raise ValueError("MelSpec: pad_mode must be 'reflect' or 'zeros', not %r" % (pad_mode,))
+        self.center, self.pad_mode = bool(center), pad_mode
+        self.top = None if top is None else float(np.float32(top))
+        self.shift, self.scale = float(np.float32(shift)), float(np.float32(scale))
+        if self.top is not None:
+            if mode == "power":
+                raise ValueError("MelSpec: top needs mode 'ln' or 'log10'")
+            if not (math.isfinite(self.top) and self.top > 0):
+                raise ValueError("MelSpec: top must be finite and greater than 0, not %r" % (top,))
+            if not math.isfinite(self.shift):
+                raise ValueError("MelSpec: shift must be finite, not %r" % (shift,))
+            if not math.isfinite(self.scale) or self.scale == 0:
+                raise ValueError("MelSpec: scale must be finite and not zero, not %r" % (scale,))
         self.window = mel_window(self.n_fft)
         self.fbank = mel_fbank(self.sample_rate, self.n_fft, self.n_mels, f_min, f_max, mel_scale, norm)
         if ctx is not None:
             h = C.c_void_p(None)
-            ctx._check(lib().clx_mel_create(ctx._h, self.n_fft, self.hop, _np_ptr(self.window), _np_ptr(self.fbank), self.n_mels,
-                                            _MEL_MODES[mode], self.floor, C.byref(h)))
+            if not self.center and self.top is None:
+                ctx._check(lib().clx_mel_create(ctx._h, self.n_fft, self.hop, _np_ptr(self.window), _np_ptr(self.fbank), self.n_mels,
+                                                _MEL_MODES[mode], self.floor, C.byref(h)))
+            else:
+                opts = _MelOpts(int(self.center), _MEL_PADS[pad_mode], int(self.top is not None), self.top or 0.0, self.shift, self.scale)
+                ctx._check(lib().clx_mel_create_ex(ctx._h, self.n_fft, self.hop, _np_ptr(self.window), _np_ptr(self.fbank), self.n_mels,
+                                                   _MEL_MODES[mode], self.floor, C.byref(opts), C.byref(h)))
             self._h = h
 
+    @classmethod
+    def whisper(cls, ctx, n_mels=80):
+        """The spec of Whisper's log_mel_spectrogram: 16 kHz, n_fft 400, hop 160, Slaney mel scale with Slaney normalisation up to
+        8 kHz, log10 with floor 1e-10, frames centred with reflection, every cell clamped to the window's maximum - 8.0, then
+        (y + 4) / 4.  read_mel(ids, starts, 3000, MelSpec.whisper(ctx)) is the encoder's [B, 80, 3000] input for 30 s crops.  The
+        filterbank is librosa's by formula (mel_fbank); Whisper's own table file is not available to this project and has not been
+        compared with it.  Whisper also drops the last of its 3001 frames; ask for the frames you want."""
+        return cls(ctx, 16000, n_fft=400, hop=160, n_mels=n_mels, f_min=0.0, f_max=8000.0, mel_scale="slaney", norm="slaney", mode="log10",
+                   floor=1e-10, center=True, pad_mode="reflect", top=8.0, shift=4.0, scale=0.25)
+
     def window_len(self, n_frames):
-        """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame)."""
-        return (int(n_frames) - 1) * self.hop + self.n_fft if int(n_frames) > 0 else 0
+        """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame); n_frames * hop for a centred spec
+        (torch.stft gives 1 + L // hop frames on such a window; read_mel takes the first n_frames)."""
+        if int(n_frames) <= 0:
+            return 0
+        return int(n_frames) * self.hop if self.center else (int(n_frames) - 1) * self.hop + self.n_fft
+
+    def valid_frames(self, valid, n_frames):
+        """valid_frames of windows with `valid` samples inside their streams (int64 array): min(ceil(valid / hop), n_frames), and
+        for a centred spec 0 where valid == 0, else min(ceil((valid + n_fft // 2) / hop), n_frames)."""
+        v = np.asarray(valid, dtype=np.int64)
+        P = self.n_fft // 2 if self.center else 0
+        return np.where(v == 0, 0, np.minimum((v + P + self.hop - 1) // self.hop, int(n_frames))).astype(np.int64)
 
     def close(self):
         if self._h is not None and self.ctx is not None and self.ctx._h:
@@ -1557,14 +1613,17 @@ class StreamSet:
         return out, torch.from_numpy(valid)
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct"):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
-        read(stream_ids, starts, (n_frames - 1) * hop + n_fft, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its
-        frames decoded -- followed by one clx_mel_windows launch on that [B, L] batch.  Returns (float32 tensor on the context's GPU:
-        [B, n_mels, n_frames] for layout "ct", [B, n_frames, n_mels] for "tc"; valid_frames): valid_frames[k] (int64 tensor) =
-        min(ceil(valid[k] / hop), n_frames) with valid[k] the window's samples inside its stream; a frame from there on is zeros,
-        whatever the mode.  The launch is queued behind read()'s, on the stream read() uses (gather_windows has the rule)."""
+        read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
+        one clx_mel_windows call on that [B, L] batch, with L = spec.window_len(n_frames): (n_frames - 1) * hop + n_fft, and for a
+        centred spec `length` or n_frames * hop (the crop the frames are centred on and reflected at; it must be longer than
+        n_fft // 2 and hold the frames: (n_frames - 1) * hop + n_fft <= length + 2 * (n_fft // 2)).  For an uncentred spec `length`
+        must be None or that L.  Returns (float32 tensor on the context's GPU: [B, n_mels, n_frames] for layout "ct",
+        [B, n_frames, n_mels] for "tc"; valid_frames): valid_frames[k] (int64 tensor) = spec.valid_frames(valid[k], n_frames) with
+        valid[k] the window's samples inside its stream; a frame from there on is zeros, whatever the mode -- the scaled silence value
+        for a spec with top.  The launches are queued behind read()'s, on the stream read() uses (gather_windows has the rule)."""
         import torch
         if layout not in _LAYOUTS:
             raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
@@ -1574,13 +1633,25 @@ class StreamSet:
             raise ValueError("read_mel: n_frames must be a whole number, not negative")
         n_frames = int(n_frames)
         L = spec.window_len(n_frames)
+        if length is not None:
+            if isinstance(length, bool) or int(length) != length or int(length) < 0:
+                raise ValueError("read_mel: length must be a whole number, not negative")
+            if not spec.center and int(length) != L:
+                raise ValueError("read_mel: length must be None or %d ((n_frames - 1) * hop + n_fft) for a spec that is not centred, not %r" % (L, length))
+            L = int(length)
+        if spec.center and n_frames > 0:
+            P = spec.n_fft // 2
+            if P >= L:
+                raise ValueError("read_mel: a centred spec needs length greater than n_fft // 2 = %d, not %d" % (P, L))
+            if (n_frames - 1) * spec.hop + spec.n_fft > L + 2 * P:
+                raise ValueError("read_mel: length %d holds %d centred frames, not %d" % (L, 1 + (L + 2 * P - spec.n_fft) // spec.hop, n_frames))
         audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1)
         B = int(audio.shape[0])
         out = torch.empty((B, spec.n_mels, n_frames) if layout == "ct" else (B, n_frames, spec.n_mels), dtype=torch.float32,
                           device=audio.device)
         valid = valid.numpy()
         self.ctx.mel_windows(spec, audio.view(B, L), valid, n_frames, _LAYOUTS[layout], out)
-        return out, torch.from_numpy(np.minimum((valid + spec.hop - 1) // spec.hop, n_frames).astype(np.int64))
+        return out, torch.from_numpy(spec.valid_frames(valid, n_frames))
 
 
 def open_streams(ctx, streams):

@@ -1570,12 +1570,17 @@ extern "C" int clx_mix_windows(clx_ctx* ctx, const void* d_src, const uint64_t* 
 
 extern "C" int clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
                               uint32_t mode, float floor, clx_mel_spec** spec) {
+    return clx_mel_create_ex(ctx, n_fft, hop, window, fbank, n_mels, mode, floor, nullptr, spec);
+}
+
+extern "C" int clx_mel_create_ex(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
+                                 uint32_t mode, float floor, const clx_mel_opts* opts, clx_mel_spec** spec) {
     if (!ctx) return CLX_API_ERROR;
     if (!spec) { ctx->last_error = "clx_mel_create: null argument"; return CLX_API_ERROR; }
     *spec = nullptr;
     clx_mel_spec* sp = new (std::nothrow) clx_mel_spec();
     if (!sp) { ctx->last_error = "clx_mel_create: out of memory"; return CLX_API_ERROR; }
-    const std::string why = clx_mel_build(n_fft, hop, window, fbank, n_mels, mode, floor, &sp->t);
+    const std::string why = clx_mel_build(n_fft, hop, window, fbank, n_mels, mode, floor, &sp->t, opts);
     if (!why.empty()) { delete sp; ctx->last_error = why; return CLX_API_ERROR; }
     sp->ctx = ctx;
     const size_t nb = sp->t.basis.size() * 4u, nf = (sp->t.fbank.size() * 4u + 15u) / 16u * 16u, ne = sp->t.ends.size() * 4u;
@@ -1608,16 +1613,18 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
                                const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream_) {
     if (!ctx) return CLX_API_ERROR;
     if (spec && spec->ctx != ctx) { ctx->last_error = "clx_mel_windows: the spec belongs to another context"; return CLX_API_ERROR; }
-    uint32_t n_groups = 0;
-    const char* why = clx_mel_check(spec ? &spec->t : nullptr, d_audio, n_windows, window_len, valid, n_frames, layout, d_out, &n_groups);
+    uint32_t n_groups = 0, n_tiles = 0;
+    const char* why = clx_mel_check(spec ? &spec->t : nullptr, d_audio, n_windows, window_len, valid, n_frames, layout, d_out, &n_groups, &n_tiles);
     if (why) { ctx->last_error = why; return CLX_API_ERROR; }
     if (n_groups == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
     if (!ctx->ev_mel_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_up, hipEventDisableTiming));
     if (!ctx->ev_mel_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_done, hipEventDisableTiming));
-    if (n_windows > ctx->mel_cap) {                            // a larger table, before anything is queued; the old one is not freed here
-        const size_t want = n_windows + n_windows / 2 + 64;
+    const bool is_c = clx_mel_is_c(spec->t);
+    const size_t words = is_c ? 3u * n_windows : n_windows;   // (valid_frames; centred or ranged: also lim and wmax)
+    if (words > ctx->mel_cap) {                                // a larger table, before anything is queued; the old one is not freed here
+        const size_t want = words + words / 2 + 64;
         uint32_t* d = nullptr; uint32_t* h = nullptr;
         if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc mel table")) return CLX_API_ERROR;
         if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc mel table")) { (void)hipFree(d); return CLX_API_ERROR; }
@@ -1627,12 +1634,24 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
         HIP_TRY(ctx, hipEventSynchronize(ctx->ev_mel_up));     // (the upload only: the earlier launch itself is not waited for)
         HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_mel_done, 0));
     }
-    clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (is_c) clx_mel_fill_c(ctx->h_mel, valid, n_windows, spec->t, window_len, n_frames);
+    else clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_up, stream));
     ctx->mel_used = true;                                      // (from here on the staging and the table are in use)
-    hipLaunchKernelGGL(clx_k_mel, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                       (const uint32_t*)ctx->d_mel, spec->dev, n_groups, window_len, n_frames, layout, (float*)d_out);
+    if (!is_c) {
+        hipLaunchKernelGGL(clx_k_mel, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                           (const uint32_t*)ctx->d_mel, spec->dev, n_groups, window_len, n_frames, layout, (float*)d_out);
+    } else {
+        hipLaunchKernelGGL(clx_k_mel_c, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                           ctx->d_mel, (uint32_t)n_windows, spec->dev, clx_mel_cargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
+        if (n_tiles) {                                         // the range step, in place, behind it
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(clx_k_mel_range, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_mel::kThreads), 0, stream, (float*)d_out,
+                               (const uint32_t*)(ctx->d_mel + 2u * n_windows), (uint64_t)spec->t.n_mels * n_frames, n_tiles,
+                               spec->t.range_width, spec->t.shift, spec->t.scale);
+        }
+    }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_done, stream));
     return CLX_OK;

@@ -29,9 +29,21 @@
 // LDS: 35 072 bytes, the staging area (16 x 512 basis floats + 16 x 36 audio floats; P, 32 x 260 floats, fits inside): four
 // workgroups share a CU's 160 KiB.
 //
-// clx_mel_build / clx_mel_check / clx_mel_fill are the host side (plain C++, shared with the wave simulator).
+// The kernel body is a template on the framing.  clx_k_mel is the plain instantiation: frame t starts at sample t * H, a dead frame is
+// +0.0.  clx_k_mel_c serves a spec that is centred and/or range scaled (claxon_hip.h, clx_mel_create_ex) and differs
+// in two places.  The audio staging address: the two loads per slice go through the index map p[t * H + n - P] (64-bit signed: t * H
+// passes 2^32) -- reflected about 0 and L - 1, or not loaded at all outside [0, valid[k]) in zero mode; lim[k] is that upper end (L
+// in reflect mode), so a tap is loaded only from [0, lim[k]) whatever the arguments are.  The last step: when ranged, a dead cell
+// takes y0 = finish(0) and not +0.0, every cell of the last pass is folded into a running maximum in an order-preserving unsigned
+// encoding of the float, the block reduces it (a wave by shuffles, the four waves through four words of the staging area) and one
+// lane folds it into wmax[k] with one atomicMax: a maximum does not depend on the order, so the result is deterministic.
+// clx_k_mel_range then clamps every cell of window k to wmax[k] - D and applies the affine, in place, behind it on the same stream:
+// pure streaming, 16-byte accesses on the window's 16-byte grid, the ragged head and tail vectors float by float.
+//
+// clx_mel_build / clx_mel_check / clx_mel_fill / clx_mel_fill_c are the host side (plain C++, shared with the wave simulator).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdint.h>
 #include <string.h>
 #include <string>
@@ -48,10 +60,18 @@ struct clx_mel_dev {
     float floor;
 };
 
+// what clx_k_mel_c needs on top of it (passed by value): P = n_fft / 2 of a centred spec (else 0), zero = 1 for CLX_MEL_PAD_ZERO
+// of a centred spec, range = 1 for a range-scaled one
+struct clx_mel_cdev {
+    uint32_t P, zero, range;
+};
+
 // a spec's tables on the host, as clx_mel_build leaves them
 struct clx_mel_tables {
     uint32_t n_fft = 0, hop = 0, n_mels = 0, n_bins = 0, n_pass = 0, n_slices = 0, mode = 0;
     float floor = 0.f;
+    uint32_t center = 0, pad = 0, range = 0;                 // clx_mel_opts (all zero: the plain spec)
+    float range_width = 0.f, shift = 0.f, scale = 0.f;
     std::vector<float> basis, fbank;
     std::vector<uint32_t> ends;
 };
@@ -61,6 +81,7 @@ namespace clx_mel {
 constexpr uint32_t kThreads = 256u, kF = 32u, kBins = 256u, kKS = 16u, kRow = 2u * kBins, kXsRow = 36u, kPRow = 260u, kMaxMels = 256u;
 constexpr uint32_t kStage = kKS * kRow + kKS * kXsRow;          // floats of the staging area (P aliases it)
 constexpr uint32_t kLdsBytes = kStage * 4u;                     // 35 072
+constexpr uint32_t kRangeVecs = 1024u;                          // 16-byte vectors of a clx_k_mel_range block: 4 per lane
 static_assert(kF * kPRow <= kStage, "P fits in the staging area");
 static_assert(2u * kLdsBytes <= 160u * 1024u, "two workgroups share a CU's LDS");
 
@@ -77,6 +98,34 @@ __device__ __forceinline__ float finish(uint32_t mode, float floor, float m) {
     return m;
 }
 
+__device__ __forceinline__ uint32_t bits_of(float v) { uint32_t b; __builtin_memcpy(&b, &v, 4); return b; }
+__device__ __forceinline__ float float_of(uint32_t b) { float v; __builtin_memcpy(&v, &b, 4); return v; }
+
+// the order-preserving encoding of a float for an unsigned atomicMax (a < b as floats <=> enc(a) < enc(b) as unsigned; -0 < +0), and back
+__device__ __forceinline__ uint32_t enc(float v) { const uint32_t b = bits_of(v); return b ^ ((b & 0x80000000u) ? 0xffffffffu : 0x80000000u); }
+__device__ __forceinline__ float dec(uint32_t e) { return float_of((e & 0x80000000u) ? e ^ 0x80000000u : ~e); }
+constexpr uint32_t kEncNegInf = 0x007fffffu;                    // enc(-inf): what the host puts into wmax[k] before the launch
+
+// a subtract, an add and a multiply that are each rounded once and never contracted (the wave simulator's host build is compiled
+// without contraction)
+#if defined(__HIP__) || defined(__HIPCC__)
+__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
+#else
+inline float sub_rn(float a, float b) { return a - b; }
+inline float add_rn(float a, float b) { return a + b; }
+inline float mul_rn(float a, float b) { return a * b; }
+#endif
+
+// The index map of a centred frame: tap i = t * H + n - P of the window p[] that continues a[0 .. L) on both sides -- by reflection
+// about 0 and L - 1, or (zero) by zeros.  Only a float of [0, lim) is loaded: lim = L in reflect mode (clx_mel_check's conditions
+// keep every reflected index inside it), lim = valid[k] in zero mode, where the window is zeros from there on anyway.
+__device__ __forceinline__ float tap(const float* a, int64_t i, uint32_t L, uint32_t lim, uint32_t zero) {
+    if (!zero) { if (i < 0) i = -i; else if (i >= (int64_t)L) i = 2 * ((int64_t)L - 1) - i; }
+    return (uint64_t)i < (uint64_t)lim ? a[i] : 0.f;
+}
+
 // cell c of the block's n_mels x kF cells: lanes run along the layout's output row
 __device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mels, uint32_t* m, uint32_t* f) {
     if (layout == CLX_WINDOW_CT) { *f = c % kF; *m = c / kF; }
@@ -86,11 +135,13 @@ __device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mel
 }  // namespace clx_mel
 
 // Block b: frame group b % n_groups of window b / n_groups (clx_mel_check gives n_groups).  `audio` is [B, L], vframes[k] =
-// valid_frames[k] <= n_frames, `out` is [B, n_mels, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_mels] (CLX_WINDOW_TC).
-extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
-                                                            uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
-                                                            float* __restrict__ out) {
-    using namespace clx_mel;
+// valid_frames[k] <= n_frames, `out` is [B, n_mels, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_mels] (CLX_WINDOW_TC).  kC: the
+// centred and/or ranged form (X, lim[k] and wmax[k] are used by it alone).
+namespace clx_mel {
+template <bool kC>
+__device__ __forceinline__ void body(const float* __restrict__ audio, const uint32_t* __restrict__ vframes,
+                                     const clx_mel_dev S, const clx_mel_cdev X, const uint32_t* __restrict__ lim, uint32_t* wmax,
+                                     uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout, float* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float s_stage[kStage];
     const uint32_t tid = threadIdx.x, k = blockIdx.x / n_groups, f0 = (blockIdx.x - k * n_groups) * kF;
     const uint32_t vf = vframes[k];
@@ -98,12 +149,15 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restr
     const uint32_t nf_live = vf > f0 ? (vf - f0 < kF ? vf - f0 : kF) : 0u;           // ... and those that are computed (<= nf_out)
     const uint32_t cells = S.n_mels * kF;
     float* const o = out + (uint64_t)k * S.n_mels * n_frames;
+    float y0 = 0.f;                                            // a dead cell: +0.0, or the silence value of a ranged spec
+    if constexpr (kC) if (X.range) y0 = finish(S.mode, S.floor, 0.f);
     if (nf_live == 0u) {
         for (uint32_t c = tid; c < cells; c += kThreads) {
             uint32_t m, f;
             cell(c, layout, S.n_mels, &m, &f);
-            if (f < nf_out) o[layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * S.n_mels + m] = 0.f;
+            if (f < nf_out) o[layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * S.n_mels + m] = kC ? y0 : 0.f;
         }
+        if constexpr (kC) if (X.range && tid == 0u) atomicMax(wmax + k, enc(y0));      // (every cell of the block is y0)
         return;
     }
     const float* const a = audio + (uint64_t)k * L;
@@ -115,6 +169,14 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restr
     // frames (tid >> 4) and (tid >> 4) + 16
     const uint32_t b_row = tid >> 7, b_col = 4u * (tid & 127u), x_kk = tid & 15u, x_f = tid >> 4;
     const uint64_t row_stride = (uint64_t)S.n_pass * kRow;
+    // kC: the taps of this lane's two frames at n = x_kk, and the end of what may be loaded
+    int64_t i0 = 0, i1 = 0;
+    uint32_t lm = 0u, emax = 0u;                               // (emax: the running maximum of the lane's cells, encoded; 0 is below all)
+    if constexpr (kC) {
+        i0 = (int64_t)((uint64_t)(f0 + x_f) * S.hop) + (int64_t)x_kk - (int64_t)X.P;
+        i1 = i0 + (int64_t)(16ull * S.hop);
+        lm = lim[k];
+    }
 
     for (uint32_t p = 0; p < S.n_pass; ++p) {
         const bool lane_live = wave_live && p * kBins + 4u * q < S.n_bins;
@@ -140,8 +202,13 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restr
                 pb7 = *reinterpret_cast<const f4*>(r + 14u * row_stride);
                 const uint32_t n = s * kKS + x_kk;
                 if (n < S.n_fft) {
-                    if (x_f < nf_live) px0 = a[(uint64_t)(f0 + x_f) * S.hop + n];
-                    if (x_f + 16u < nf_live) px1 = a[(uint64_t)(f0 + x_f + 16u) * S.hop + n];
+                    if constexpr (kC) {
+                        if (x_f < nf_live) px0 = tap(a, i0 + (int64_t)(s * kKS), L, lm, X.zero);
+                        if (x_f + 16u < nf_live) px1 = tap(a, i1 + (int64_t)(s * kKS), L, lm, X.zero);
+                    } else {
+                        if (x_f < nf_live) px0 = a[(uint64_t)(f0 + x_f) * S.hop + n];
+                        if (x_f + 16u < nf_live) px1 = a[(uint64_t)(f0 + x_f + 16u) * S.hop + n];
+                    }
                 }
             }
             if (s > 0u && lane_live) {
@@ -198,28 +265,115 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restr
             cell(c, layout, S.n_mels, &m, &f);
             if (f >= nf_out) continue;
             float* const at = o + (layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * S.n_mels + m);
-            if (f >= nf_live) { if (last) *at = 0.f; continue; }
+            if (f >= nf_live) {
+                if (last) {
+                    *at = kC ? y0 : 0.f;
+                    if constexpr (kC) { const uint32_t e = enc(y0); emax = e > emax ? e : emax; }
+                }
+                continue;
+            }
             float acc = p ? *at : 0.f;                         // (this lane's own store of the pass before)
             const uint32_t e0 = S.ends[2u * m], e1 = S.ends[2u * m + 1u];
             const uint32_t lo = e0 > j0 ? e0 : j0, hi = e1 < j1 ? e1 : j1;
             const float* const fb = S.fbank + (uint64_t)m * S.n_bins;
             const float* const pr = P + f * kPRow;
             for (uint32_t j = lo; j < hi; ++j) acc = fmaf(fb[j], pr[j - j0], acc);
-            *at = last ? finish(S.mode, S.floor, acc) : acc;
+            if constexpr (kC) {
+                if (last) {
+                    const float y = finish(S.mode, S.floor, acc);
+                    const uint32_t e = enc(y);
+                    emax = e > emax ? e : emax;
+                    *at = y;
+                } else *at = acc;
+            } else *at = last ? finish(S.mode, S.floor, acc) : acc;
+        }
+    }
+    if constexpr (kC) {
+        if (X.range) {                                         // (uniform over the block: every lane is still here)
+            for (int d = 32; d > 0; d >>= 1) { const uint32_t e = __shfl_xor(emax, d); emax = e > emax ? e : emax; }
+            uint32_t* const red = reinterpret_cast<uint32_t*>(s_stage);
+            __syncthreads();                                   // (the last pass's P has been read)
+            if (q == 0u) red[w] = emax;
+            __syncthreads();
+            if (tid == 0u) {
+                const uint32_t e01 = red[0] > red[1] ? red[0] : red[1], e23 = red[2] > red[3] ? red[2] : red[3];
+                atomicMax(wmax + k, e01 > e23 ? e01 : e23);
+            }
+        }
+    }
+}
+}  // namespace clx_mel
+
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
+                                                            uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
+                                                            float* __restrict__ out) {
+    clx_mel::body<false>(audio, vframes, S, clx_mel_cdev(), nullptr, nullptr, n_groups, L, n_frames, layout, out);
+}
+
+// The centred and/or ranged form.  `table` is the call's device table: vframes[B], then lim[B] (the end of what a tap may load of
+// window k: valid[k] in zero mode, L otherwise), then wmax[B] (ranged: enc(-inf) on entry, the encoded maximum of window k's cells
+// when the launch has finished).
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel_c(const float* __restrict__ audio, uint32_t* table, uint32_t n_windows, clx_mel_dev S,
+                                                              clx_mel_cdev X, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
+                                                              float* __restrict__ out) {
+    clx_mel::body<true>(audio, table, S, X, table + n_windows, table + 2u * (uint64_t)n_windows, n_groups, L, n_frames, layout, out);
+}
+
+// The range step, in place: out[k][c] = fl32(fl32(max(out[k][c], fl32(max_k - D)) + shift) * scale) for the `cells` cells of window
+// k, max_k = dec(wmax[k]).  Block b: tile b % n_tiles of window b / n_tiles; a tile is kRangeVecs vectors of the window's 16-byte
+// grid (vector v holds the window's floats 4 v - head .. + 3, head = the floats of its first vector that lie in front of it), a
+// whole vector is one 16-byte load and store, a ragged one (the window's head and tail) goes float by float.
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel_range(float* out, const uint32_t* __restrict__ wmax, uint64_t cells, uint32_t n_tiles,
+                                                                  float D, float shift, float scale) {
+    using namespace clx_mel;
+    const uint32_t k = blockIdx.x / n_tiles, t = blockIdx.x - k * n_tiles;
+    float* const o = out + (uint64_t)k * cells;
+    const uint32_t head = (uint32_t)(((uintptr_t)o >> 2) & 3u);
+    const uint64_t vectors = (cells + head + 3u) >> 2;
+    const float lo = sub_rn(dec(wmax[k]), D);
+    for (uint32_t i = 0; i < kRangeVecs / kThreads; ++i) {
+        const uint64_t v = (uint64_t)t * kRangeVecs + i * kThreads + threadIdx.x;
+        if (v >= vectors) break;
+        const int64_t e0 = (int64_t)(v * 4u) - (int64_t)head;
+        float* const p = o + e0;                               // 16-byte aligned
+        if (e0 >= 0 && (uint64_t)e0 + 4u <= cells) {
+            f4 x = *reinterpret_cast<const f4*>(p);
+            x[0] = mul_rn(add_rn(fmaxf(x[0], lo), shift), scale);
+            x[1] = mul_rn(add_rn(fmaxf(x[1], lo), shift), scale);
+            x[2] = mul_rn(add_rn(fmaxf(x[2], lo), shift), scale);
+            x[3] = mul_rn(add_rn(fmaxf(x[3], lo), shift), scale);
+            *reinterpret_cast<f4*>(p) = x;
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (e0 + j >= 0 && (uint64_t)(e0 + j) < cells) p[j] = mul_rn(add_rn(fmaxf(p[j], lo), shift), scale);
         }
     }
 }
 
 // The host side of clx_mel_create: checks the spec's arguments (empty: fine, else the text for clx_last_error) and builds its
 // tables: the basis in double, rounded once, in the padded layout the kernel stages from; a copy of the filterbank; each row's ends.
+// `opts` (clx_mel_create_ex; nullptr: all zero) is checked and copied into the tables.
 inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels, uint32_t mode,
-                                 float floor, clx_mel_tables* t) {
+                                 float floor, clx_mel_tables* t, const clx_mel_opts* opts = nullptr) {
     if (n_fft < 2u || n_fft > 2048u) return "clx_mel_create: n_fft must be 2..2048";
     if (hop < 1u) return "clx_mel_create: hop must be at least 1";
     if (n_mels < 1u || n_mels > clx_mel::kMaxMels) return "clx_mel_create: n_mels must be 1..256";
     if (mode != CLX_MEL_POWER && mode != CLX_MEL_LN && mode != CLX_MEL_LOG10) return "clx_mel_create: mode must be CLX_MEL_POWER, CLX_MEL_LN or CLX_MEL_LOG10";
     if (mode != CLX_MEL_POWER && !(floor > 0.f)) return "clx_mel_create: floor must be greater than 0 in a log mode";
     if (!window || !fbank || !t) return "clx_mel_create: null argument";
+    if (opts) {
+        if (opts->center > 1u) return "clx_mel_create_ex: center must be 0 or 1";
+        if (opts->range > 1u) return "clx_mel_create_ex: range must be 0 or 1";
+        if (opts->pad != CLX_MEL_PAD_REFLECT && opts->pad != CLX_MEL_PAD_ZERO) return "clx_mel_create_ex: pad must be CLX_MEL_PAD_REFLECT or CLX_MEL_PAD_ZERO";
+        if (opts->range) {
+            if (mode == CLX_MEL_POWER) return "clx_mel_create_ex: range scaling needs a log mode";
+            if (!std::isfinite(opts->range_width) || !(opts->range_width > 0.f)) return "clx_mel_create_ex: range_width must be finite and greater than 0";
+            if (!std::isfinite(opts->shift)) return "clx_mel_create_ex: shift must be finite";
+            if (!std::isfinite(opts->scale) || opts->scale == 0.f) return "clx_mel_create_ex: scale must be finite and not zero";
+        }
+        t->center = opts->center; t->pad = opts->pad; t->range = opts->range;
+        t->range_width = opts->range_width; t->shift = opts->shift; t->scale = opts->scale;
+    }
     using namespace clx_mel;
     const uint32_t N = n_fft, J = N / 2u + 1u;
     t->n_fft = N; t->hop = hop; t->n_mels = n_mels; t->n_bins = J; t->mode = mode; t->floor = floor;
@@ -248,28 +402,60 @@ inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* wind
 }
 
 // The host side of clx_mel_windows: checks the arguments (nullptr: fine, else the text for clx_last_error) and gives the launch
-// shape: *n_groups frame groups per window (0: nothing to launch), n_windows * *n_groups blocks of clx_mel::kThreads.
+// shape: *n_groups frame groups per window (0: nothing to launch), n_windows * *n_groups blocks of clx_mel::kThreads.  A centred
+// spec is held to torch.stft's frame count (P = n_fft / 2 < window_len, and the last frame ends inside window_len + 2 P); a ranged
+// one also gets *n_tiles, the tiles per window of clx_k_mel_range (n_windows * *n_tiles blocks).
 inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, size_t n_windows, uint32_t window_len, const uint32_t* valid,
-                                 uint32_t n_frames, uint32_t layout, const void* out, uint32_t* n_groups) {
+                                 uint32_t n_frames, uint32_t layout, const void* out, uint32_t* n_groups, uint32_t* n_tiles = nullptr) {
     *n_groups = 0;
+    if (n_tiles) *n_tiles = 0;
     if (!t) return "clx_mel_windows: null spec";
     if (layout != CLX_WINDOW_TC && layout != CLX_WINDOW_CT) return "clx_mel_windows: layout must be CLX_WINDOW_TC or CLX_WINDOW_CT";
     if (n_windows == 0 || n_frames == 0) return nullptr;
     if (!audio || !valid || !out) return "clx_mel_windows: null argument";
-    if ((uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len is less than (n_frames - 1) * hop + n_fft";
+    if (t->center) {
+        const uint64_t P = t->n_fft / 2u;
+        if (P >= window_len) return "clx_mel_windows: a centred spec needs n_fft / 2 less than window_len";
+        if ((uint64_t)window_len + 2u * P < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len + 2 * (n_fft / 2) is less than (n_frames - 1) * hop + n_fft";
+    } else if ((uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len is less than (n_frames - 1) * hop + n_fft";
     for (size_t k = 0; k < n_windows; ++k)
         if (valid[k] > window_len) return "clx_mel_windows: valid[k] is larger than window_len";
     const uint64_t groups = ((uint64_t)n_frames + clx_mel::kF - 1u) / clx_mel::kF;
     if (groups * (uint64_t)n_windows > 0x7fffffffull) return "clx_mel_windows: too many windows in one call";
+    if (t->range) {                                            // (a window's 16-byte grid has at most (cells + 6) / 4 vectors)
+        const uint64_t cells = (uint64_t)t->n_mels * n_frames, tiles = (((cells + 6u) >> 2) + clx_mel::kRangeVecs - 1u) / clx_mel::kRangeVecs;
+        if (tiles * (uint64_t)n_windows > 0x7fffffffull) return "clx_mel_windows: too many windows in one call";
+        if (n_tiles) *n_tiles = (uint32_t)tiles;
+    }
     *n_groups = (uint32_t)groups;
     return nullptr;
 }
 
-// valid_frames[k] = clamp(ceil(valid[k] / hop), 0, n_frames)
-inline void clx_mel_fill(uint32_t* vframes, const uint32_t* valid, size_t n_windows, uint32_t hop, uint32_t n_frames) {
+// valid_frames[k] = clamp(ceil(valid[k] / hop), 0, n_frames); centred by P: 0 for valid[k] == 0, else min(n_frames,
+// ceil((valid[k] + P) / hop)), the frames with t * hop - P < valid[k]
+inline void clx_mel_fill(uint32_t* vframes, const uint32_t* valid, size_t n_windows, uint32_t hop, uint32_t n_frames, uint32_t P = 0u) {
     for (size_t k = 0; k < n_windows; ++k) {
-        const uint64_t v = ((uint64_t)valid[k] + hop - 1u) / hop;
+        const uint64_t v = valid[k] ? ((uint64_t)valid[k] + P + hop - 1u) / hop : 0u;
         vframes[k] = v < n_frames ? (uint32_t)v : n_frames;
+    }
+}
+
+inline bool clx_mel_is_c(const clx_mel_tables& t) { return t.center != 0u || t.range != 0u; }
+
+inline clx_mel_cdev clx_mel_cargs(const clx_mel_tables& t) {
+    clx_mel_cdev x;
+    x.P = t.center ? t.n_fft / 2u : 0u; x.zero = t.center && t.pad == CLX_MEL_PAD_ZERO ? 1u : 0u; x.range = t.range;
+    return x;
+}
+
+// clx_k_mel_c's table, 3 * n_windows words: valid_frames, then lim (valid[k] for zero padding, else window_len), then wmax
+// (the encoding of -inf, so that the device needs no memset)
+inline void clx_mel_fill_c(uint32_t* table, const uint32_t* valid, size_t n_windows, const clx_mel_tables& t, uint32_t window_len, uint32_t n_frames) {
+    const clx_mel_cdev x = clx_mel_cargs(t);
+    clx_mel_fill(table, valid, n_windows, t.hop, n_frames, x.P);
+    for (size_t k = 0; k < n_windows; ++k) {
+        table[n_windows + k] = x.zero ? valid[k] : window_len;
+        table[2u * n_windows + k] = clx_mel::kEncNegInf;
     }
 }
 

@@ -479,13 +479,48 @@ enum { CLX_MEL_POWER = 0, CLX_MEL_LN = 1, CLX_MEL_LOG10 = 2 };
 typedef struct clx_mel_spec clx_mel_spec;
 int  clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
                     uint32_t mode, float floor, clx_mel_spec** spec);
+/* Centred frames and per-window range scaling (clx_k_mel_c, clx_k_mel_range).  clx_mel_create_ex is
+ * clx_mel_create with options; opts == NULL or all zero is clx_mel_create itself: the same tables, kernel and words.
+ *
+ *   center, pad   With P = n_fft / 2 (integer division) frame t of window k is x[n] = p[t*H + n - P], n = 0..N-1, where p
+ *              continues the dense window a[k][0 .. L) on both sides:  p[i] = a[k][i] for 0 <= i < L;  for i < 0, p[i] = a[k][-i]
+ *              (CLX_MEL_PAD_REFLECT) or 0 (CLX_MEL_PAD_ZERO);  for i >= L, p[i] = a[k][2(L-1) - i] (reflect) or 0 (zero).  The
+ *              reflection is about the window's own ends 0 and L-1, not about valid[k]: what a model sees on a crop that was
+ *              zero-padded to L (torch.stft(center=True) on that crop).  Everything after x[n] is the definition above, in the
+ *              kernel's same order of sums, so a centred call is bit-equal to the uncentred one on the batch padded by P on both
+ *              sides on the host (with valid[k] + P for valid[k] > 0).  clx_mel_windows requires P < window_len and
+ *              (n_frames-1)*H + N <= window_len + 2P -- torch.stft's frame count, n_frames <= 1 + floor(L / H) for even N -- in
+ *              place of the uncentred condition.
+ *   validity   valid_frames[k] = 0 if valid[k] == 0, else min(n_frames, ceil((valid[k] + P) / H)): the frames with
+ *              t*H - P < valid[k].  A frame at or past it is dead: not computed, whatever a reflection would bring into it.
+ *   loads      Zero mode: a tap outside [0, valid[k]) is taken as +0.0 and not loaded (the window is zeros from valid[k] on, so
+ *              this changes no word).  Reflect mode: a live frame may load any float of [0, L).  Nothing outside the [B, L]
+ *              batch is read in either mode.
+ *   range      Log modes only.  Let y be the mode's output of a live cell, and let a dead cell take y0 = logf(floor) /
+ *              log10f(floor) as the device computes it for M = 0 (a dead frame and a computed frame of zeros are the same
+ *              words).  max_k is the maximum of y over all n_frames * n_mels cells of window k, dead ones included.  Then
+ *              out = fl32(fl32(max(y, fl32(max_k - range_width)) + shift) * scale): the subtract, the add and the multiply are
+ *              each rounded once, nothing is contracted.  A ranged call writes no +0.0 padding frames: a dead cell holds the
+ *              scaled silence value.  Whisper: log10, floor 1e-10, range_width 8, shift 4, scale 0.25; AmplitudeToDB(top_db=80)
+ *              on power: log10, range_width 8, shift 0, scale 10.  The maximum is found by the feature launch itself (one
+ *              unsigned atomicMax per block on an order-preserving encoding: order independent, hence deterministic) and applied
+ *              by a second launch behind it on the same stream, in place.  With range == 0 nothing of the last step changes.
+ *
+ * CLX_API_ERROR also for: center or range other than 0 or 1, an unknown pad, and with range == 1: CLX_MEL_POWER, a range_width
+ * that is not finite and > 0, a shift that is not finite, a scale that is not finite or is zero. */
+enum { CLX_MEL_PAD_REFLECT = 0, CLX_MEL_PAD_ZERO = 1 };
+typedef struct { uint32_t center, pad, range; float range_width, shift, scale; } clx_mel_opts;
+int  clx_mel_create_ex(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
+                       uint32_t mode, float floor, const clx_mel_opts* opts, clx_mel_spec** spec);
 void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
 /* The features of d_audio [n_windows][window_len] (device, float32) into d_out (device, float32), asynchronously on `stream`
  * (NULL: the context's).  valid is a host array; it is staged like the window table of clx_gather_windows: pinned staging, a
  * table that has to grow is replaced before anything is queued, one event behind the upload and one behind the launch, so the
  * call returns without waiting for the device and valid may be reused at once.  CLX_API_ERROR for a null argument, a spec of
  * another context, window_len < (n_frames-1)*hop + n_fft, a valid[k] > window_len and an unknown layout.  n_windows == 0 or
- * n_frames == 0 succeeds and launches nothing. */
+ * n_frames == 0 succeeds and launches nothing.  The spec decides the kernel, the length condition and the valid_frames rule: a
+ * centred or ranged spec runs clx_k_mel_c (its table also carries, per window, the end of what may be loaded and the encoded
+ * maximum, initialised by the upload), a ranged one clx_k_mel_range behind it. */
 int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
                      const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
