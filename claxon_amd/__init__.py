@@ -101,7 +101,7 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
-    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_destroy", "clx_mel_windows",
+    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_destroy", "clx_mel_windows",
 ]
 
 
@@ -185,6 +185,8 @@ def lib():
     L.clx_mix_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_mel_create.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(vp)]
     L.clx_mel_create_ex.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, vp, C.POINTER(vp)]
+    L.clx_mel_create_framed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
+                                        C.POINTER(vp)]
     L.clx_mel_destroy.argtypes = [vp, vp]
     L.clx_mel_destroy.restype = None
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
@@ -1252,6 +1254,10 @@ class _MelOpts(C.Structure):             # clx_mel_opts
                 ("scale", C.c_float)]
 
 
+class _MelFrameOpts(C.Structure):        # clx_mel_frame_opts
+    _fields_ = [("remove_dc", C.c_uint32), ("whole_frames", C.c_uint32), ("preemph", C.c_float)]
+
+
 def _hz_to_mel(f, scale):
     f = np.asarray(f, dtype=np.float64)
     if scale == "htk":
@@ -1306,6 +1312,53 @@ def mel_fbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None, mel_scale="htk"
     return fb
 
 
+KALDI_WINDOWS = ("povey", "hanning", "hamming", "rectangular")
+FLT_EPSILON = float(np.finfo(np.float32).eps)
+
+
+def mel_window_kaldi(window_type, win_length, scale=1.0):
+    """Kaldi's symmetric frame window of win_length points times `scale`, in double, rounded once to float32: "povey"
+    (0.5 - 0.5 cos(2 pi n / (win_length - 1))) ^ 0.85, "hanning" (the same without the power), "hamming" 0.54 - 0.46 cos(..) or
+    "rectangular"."""
+    if window_type not in KALDI_WINDOWS:
+        raise ValueError("mel_window_kaldi: window_type must be one of %s, not %r" % (", ".join(KALDI_WINDOWS), window_type))
+    Nw = int(win_length)
+    if Nw < 1 or (Nw < 2 and window_type != "rectangular"):
+        raise ValueError("mel_window_kaldi: a %s window needs at least %d points" % (window_type, 1 if window_type == "rectangular" else 2))
+    cosine = np.cos(2.0 * np.pi * np.arange(Nw, dtype=np.float64) / max(Nw - 1, 1))
+    w = {"povey": lambda: (0.5 - 0.5 * cosine) ** 0.85, "hanning": lambda: 0.5 - 0.5 * cosine, "hamming": lambda: 0.54 - 0.46 * cosine,
+         "rectangular": lambda: np.ones(Nw, dtype=np.float64)}[window_type]()
+    return (w * float(scale)).astype(np.float32)
+
+
+def mel_fbank_kaldi(sample_rate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
+    """Kaldi's mel filterbank [n_mels, n_fft // 2] (float32, built in double and rounded once; the Nyquist bin is not used).  With
+    mel(f) = 1127 ln(1 + f / 700), a high_freq <= 0 added to the Nyquist frequency and delta = (mel(high) - mel(low)) / (n_mels + 1),
+    band b has left = mel(low) + b delta, centre = left + delta and right = centre + delta: the triangles are linear in mel, not in
+    Hz.  Bin i lies at m = mel(i sample_rate / n_fft) and weighs (m - left) / (centre - left) for left < m <= centre,
+    (right - m) / (right - centre) for centre < m < right, else 0.  A band without a bin is allowed (with many bands the lowest are
+    empty, in Kaldi too)."""
+    sample_rate, n_fft, n_mels = float(sample_rate), int(n_fft), int(n_mels)
+    nyquist = 0.5 * sample_rate
+    low, high = float(low_freq), float(high_freq)
+    if high <= 0.0:
+        high += nyquist
+    if n_fft < 2 or n_mels < 1:
+        raise ValueError("mel_fbank_kaldi: need n_fft >= 2 and n_mels >= 1")
+    if not (sample_rate > 0 and 0.0 <= low < high <= nyquist):
+        raise ValueError("mel_fbank_kaldi: need sample_rate > 0 and 0 <= low_freq < high_freq <= sample_rate / 2 (a high_freq <= 0 counts from there)")
+    mel = lambda f: 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+    mel_lo, mel_hi = float(mel(low)), float(mel(high))
+    delta = (mel_hi - mel_lo) / (n_mels + 1)
+    left = (mel_lo + np.arange(n_mels, dtype=np.float64) * delta)[:, None]
+    centre = left + delta
+    right = centre + delta
+    m = mel(np.arange(n_fft // 2, dtype=np.float64) * (sample_rate / n_fft))[None, :]
+    up, down = (m - left) / (centre - left), (right - m) / (right - centre)
+    fb = np.where((m > left) & (m <= centre), up, np.where((m > centre) & (m < right), down, 0.0))
+    return np.ascontiguousarray(fb.astype(np.float32))
+
+
 class MelSpec:
     """A feature spec for Context.mel_windows and StreamSet.read_mel (clx_mel_create, claxon_hip.h): frames of n_fft samples every
     `hop`, the periodic Hann window (.window), a triangular mel filterbank (.fbank, [n_mels, n_fft // 2 + 1]: mel_fbank) and the last
@@ -1318,7 +1371,11 @@ class MelSpec:
     samples on both sides, by reflection about the window's own ends (pad_mode="reflect") or by zeros ("zeros").  top=D (log modes)
     turns range scaling on: every cell is clamped to the window's maximum minus D, then (y + shift) * scale; a frame past the
     window's valid samples then holds the scaled silence value and not zeros.  (clx_mel_create_ex, claxon_hip.h, has both in full.)
-    Without them the spec is what it always was."""
+    Without them the spec is what it always was.
+
+    MelSpec.framed() builds a spec from a window and a filterbank of the caller's, with a frame shorter than the transform, each
+    frame's mean removed and pre-emphasised before the window, a bank over the first bins only and whole frames counted
+    (clx_mel_create_framed); MelSpec.kaldi() is Kaldi's fbank that way."""
 
     def __init__(self, ctx, sample_rate, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, mode="ln",
                  floor=1e-10, center=False, pad_mode="reflect", top=None, shift=0.0, scale=1.0):
@@ -1350,6 +1407,7 @@ class MelSpec:
                 raise ValueError("MelSpec: shift must be finite, not %r" % (shift,))
             if not math.isfinite(self.scale) or self.scale == 0:
                 raise ValueError("MelSpec: scale must be finite and not zero, not %r" % (scale,))
+        self.win_length, self.n_bins, self.remove_dc, self.preemph, self.whole_frames = self.n_fft, self.n_fft // 2 + 1, False, 0.0, False
         self.window = mel_window(self.n_fft)
         self.fbank = mel_fbank(self.sample_rate, self.n_fft, self.n_mels, f_min, f_max, mel_scale, norm)
         if ctx is not None:
@@ -1373,17 +1431,98 @@ class MelSpec:
         return cls(ctx, 16000, n_fft=400, hop=160, n_mels=n_mels, f_min=0.0, f_max=8000.0, mel_scale="slaney", norm="slaney", mode="log10",
                    floor=1e-10, center=True, pad_mode="reflect", top=8.0, shift=4.0, scale=0.25)
 
+    @classmethod
+    def framed(cls, ctx, sample_rate, n_fft, win_length, hop, window, fbank, mode="ln", floor=1e-10, remove_dc=False, preemph=0.0,
+               whole_frames=False):
+        """The general framed spec (clx_mel_create_framed, claxon_hip.h): frames of win_length <= n_fft samples every `hop`, each
+        with its own mean removed (remove_dc) and pre-emphasised by `preemph` (0: none; the first tap refers to the frame's own first
+        sample), then `window` [win_length] and an n_fft-point transform of which the first n_bins bins go through `fbank`
+        [n_mels, n_bins], n_bins <= n_fft // 2 + 1; rows of the bank may be all zero.  whole_frames counts only frames that lie
+        inside a window's valid samples.  The tables are taken as float32.  ctx=None keeps the tables only."""
+        for name, v in (("sample_rate", sample_rate), ("n_fft", n_fft), ("win_length", win_length), ("hop", hop)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v:
+                raise ValueError("MelSpec.framed: %s must be a whole number, not %r" % (name, v))
+        if mode not in _MEL_MODES:
+            raise ValueError("MelSpec.framed: mode must be 'ln', 'log10' or 'power', not %r" % (mode,))
+        self = cls.__new__(cls)
+        self.ctx, self._h = ctx, None
+        self.sample_rate, self.n_fft, self.win_length, self.hop = int(sample_rate), int(n_fft), int(win_length), int(hop)
+        if not 2 <= self.n_fft <= 2048 or not 1 <= self.win_length <= self.n_fft or not 1 <= self.hop < 1 << 32 or self.sample_rate < 1:
+            raise ValueError("MelSpec.framed: need n_fft in 2..2048, win_length in 1..n_fft, hop >= 1 and sample_rate >= 1")
+        self.window = np.ascontiguousarray(window, dtype=np.float32)
+        self.fbank = np.ascontiguousarray(fbank, dtype=np.float32)
+        if self.window.shape != (self.win_length,):
+            raise ValueError("MelSpec.framed: window must have win_length = %d points, not shape %r" % (self.win_length, self.window.shape))
+        if self.fbank.ndim != 2 or not 1 <= self.fbank.shape[0] <= 256 or not 1 <= self.fbank.shape[1] <= self.n_fft // 2 + 1:
+            raise ValueError("MelSpec.framed: fbank must be [n_mels in 1..256, n_bins in 1..n_fft // 2 + 1], not shape %r" % (self.fbank.shape,))
+        self.n_mels, self.n_bins = int(self.fbank.shape[0]), int(self.fbank.shape[1])
+        self.mode, self.floor = mode, float(np.float32(floor))
+        if mode != "power" and not self.floor > 0:
+            raise ValueError("MelSpec.framed: floor must be greater than 0 in mode %r" % mode)
+        for name, v in (("remove_dc", remove_dc), ("whole_frames", whole_frames)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError("MelSpec.framed: %s must be True or False, not %r" % (name, v))
+        self.remove_dc, self.whole_frames, self.preemph = bool(remove_dc), bool(whole_frames), float(np.float32(preemph))
+        if not (math.isfinite(self.preemph) and 0.0 <= self.preemph <= 1.0):
+            raise ValueError("MelSpec.framed: preemph must be finite and in 0..1, not %r" % (preemph,))
+        self.center, self.pad_mode, self.top, self.shift, self.scale = False, "reflect", None, 0.0, 1.0
+        if ctx is not None:
+            h = C.c_void_p(None)
+            opts = _MelFrameOpts(int(self.remove_dc), int(self.whole_frames), self.preemph)
+            ctx._check(lib().clx_mel_create_framed(ctx._h, self.n_fft, self.win_length, self.hop, _np_ptr(self.window), _np_ptr(self.fbank),
+                                                   self.n_bins, self.n_mels, _MEL_MODES[mode], self.floor, C.byref(opts), C.byref(h)))
+            self._h = h
+        return self
+
+    _KALDI_REFUSED = dict(dither=0.0, use_energy=False, snip_edges=True, vtln_warp=1.0, htk_compat=False)
+
+    @classmethod
+    def kaldi(cls, ctx, sample_rate=16000, n_mels=80, frame_length_ms=25.0, frame_shift_ms=10.0, low_freq=20.0, high_freq=0.0,
+              preemphasis=0.97, remove_dc_offset=True, window_type="povey", scale=32768.0, **refused):
+        """Kaldi's fbank (torchaudio.compliance.kaldi.fbank, kaldi-native-fbank, lhotse's Fbank) with its defaults: frames of
+        frame_length_ms every frame_shift_ms (400 and 160 samples at 16 kHz), the frame's mean removed, pre-emphasis 0.97, the povey
+        window, a transform of the next power of two (512; at most 2048) of which the Nyquist bin is not used, n_mels triangles that
+        are linear in mel from low_freq to the Nyquist frequency + high_freq (mel_fbank_kaldi), ln with floor FLT_EPSILON, and only
+        whole frames counted (snip_edges).  Kaldi works on samples in the int16 range: the window is multiplied by `scale` (32768)
+        in double before its one rounding, and as the conditioning is linear a power-of-two scale gives what Kaldi gives on the
+        int16-range input bit for bit.  read_mel(ids, starts, n_frames, MelSpec.kaldi(ctx)) is [B, n_mels, n_frames] ("tc":
+        Kaldi's own [n_frames, n_mels]).  dither, use_energy, snip_edges=False, vtln_warp and htk_compat are refused by name.  The
+        definition restates Kaldi's and has not been compared with a Kaldi binary."""
+        for name, v in refused.items():
+            if name not in cls._KALDI_REFUSED:
+                raise TypeError("MelSpec.kaldi: unknown argument %r" % name)
+            if isinstance(v, bool) != isinstance(cls._KALDI_REFUSED[name], bool) or v != cls._KALDI_REFUSED[name]:
+                raise ValueError("MelSpec.kaldi: %s=%r is not supported (only %r)" % (name, v, cls._KALDI_REFUSED[name]))
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float, np.integer, np.floating)) or int(sample_rate) != sample_rate or sample_rate < 1:
+            raise ValueError("MelSpec.kaldi: sample_rate must be a whole number from 1 up, not %r" % (sample_rate,))
+        win_length, hop = int(sample_rate * 0.001 * float(frame_length_ms)), int(sample_rate * 0.001 * float(frame_shift_ms))
+        if not 2 <= win_length <= 2048 or hop < 1:
+            raise ValueError("MelSpec.kaldi: the frame must be 2..2048 samples and the shift at least 1, not %d and %d" % (win_length, hop))
+        n_fft = 1 << (win_length - 1).bit_length()
+        if not (math.isfinite(float(scale)) and float(scale) > 0):
+            raise ValueError("MelSpec.kaldi: scale must be finite and greater than 0, not %r" % (scale,))
+        if not isinstance(remove_dc_offset, (bool, np.bool_)):
+            raise ValueError("MelSpec.kaldi: remove_dc_offset must be True or False, not %r" % (remove_dc_offset,))
+        window = mel_window_kaldi(window_type, win_length, scale)
+        fbank = mel_fbank_kaldi(sample_rate, n_fft, n_mels, low_freq, high_freq)
+        return cls.framed(ctx, sample_rate, n_fft, win_length, hop, window, fbank, mode="ln", floor=FLT_EPSILON, remove_dc=bool(remove_dc_offset),
+                          preemph=preemphasis, whole_frames=True)
+
     def window_len(self, n_frames):
-        """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame); n_frames * hop for a centred spec
-        (torch.stft gives 1 + L // hop frames on such a window; read_mel takes the first n_frames)."""
+        """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame; win_length in place of n_fft for a
+        framed spec); n_frames * hop for a centred spec (torch.stft gives 1 + L // hop frames on such a window; read_mel takes the
+        first n_frames)."""
         if int(n_frames) <= 0:
             return 0
-        return int(n_frames) * self.hop if self.center else (int(n_frames) - 1) * self.hop + self.n_fft
+        return int(n_frames) * self.hop if self.center else (int(n_frames) - 1) * self.hop + self.win_length
 
     def valid_frames(self, valid, n_frames):
         """valid_frames of windows with `valid` samples inside their streams (int64 array): min(ceil(valid / hop), n_frames), and
-        for a centred spec 0 where valid == 0, else min(ceil((valid + n_fft // 2) / hop), n_frames)."""
+        for a centred spec 0 where valid == 0, else min(ceil((valid + n_fft // 2) / hop), n_frames).  A spec that counts whole
+        frames: 0 where valid < win_length, else min(1 + (valid - win_length) // hop, n_frames)."""
         v = np.asarray(valid, dtype=np.int64)
+        if self.whole_frames:
+            return np.where(v < self.win_length, 0, np.minimum(1 + (v - self.win_length) // self.hop, int(n_frames))).astype(np.int64)
         P = self.n_fft // 2 if self.center else 0
         return np.where(v == 0, 0, np.minimum((v + P + self.hop - 1) // self.hop, int(n_frames))).astype(np.int64)
 

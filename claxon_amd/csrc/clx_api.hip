@@ -1573,14 +1573,16 @@ extern "C" int clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const 
     return clx_mel_create_ex(ctx, n_fft, hop, window, fbank, n_mels, mode, floor, nullptr, spec);
 }
 
-extern "C" int clx_mel_create_ex(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
-                                 uint32_t mode, float floor, const clx_mel_opts* opts, clx_mel_spec** spec) {
+// clx_mel_create_ex and clx_mel_create_framed: the tables of either, uploaded
+static int clx_mel_create_any(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank,
+                              uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_opts* opts,
+                              const clx_mel_frame_opts* fopts, clx_mel_spec** spec) {
     if (!ctx) return CLX_API_ERROR;
     if (!spec) { ctx->last_error = "clx_mel_create: null argument"; return CLX_API_ERROR; }
     *spec = nullptr;
     clx_mel_spec* sp = new (std::nothrow) clx_mel_spec();
     if (!sp) { ctx->last_error = "clx_mel_create: out of memory"; return CLX_API_ERROR; }
-    const std::string why = clx_mel_build(n_fft, hop, window, fbank, n_mels, mode, floor, &sp->t, opts);
+    const std::string why = clx_mel_build_framed(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, opts, fopts);
     if (!why.empty()) { delete sp; ctx->last_error = why; return CLX_API_ERROR; }
     sp->ctx = ctx;
     const size_t nb = sp->t.basis.size() * 4u, nf = (sp->t.fbank.size() * 4u + 15u) / 16u * 16u, ne = sp->t.ends.size() * 4u;
@@ -1596,6 +1598,17 @@ extern "C" int clx_mel_create_ex(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, con
     ctx->mel_specs.push_back(sp);
     *spec = sp;
     return CLX_OK;
+}
+
+extern "C" int clx_mel_create_ex(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
+                                 uint32_t mode, float floor, const clx_mel_opts* opts, clx_mel_spec** spec) {
+    return clx_mel_create_any(ctx, n_fft, n_fft, hop, window, fbank, n_fft / 2u + 1u, n_mels, mode, floor, opts, nullptr, spec);
+}
+
+extern "C" int clx_mel_create_framed(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank,
+                                     uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_frame_opts* opts,
+                                     clx_mel_spec** spec) {
+    return clx_mel_create_any(ctx, n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, nullptr, opts, spec);
 }
 
 extern "C" void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec) {
@@ -1635,11 +1648,14 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
         HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_mel_done, 0));
     }
     if (is_c) clx_mel_fill_c(ctx->h_mel, valid, n_windows, spec->t, window_len, n_frames);
-    else clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames);
+    else clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames, 0u, clx_mel_whole(spec->t));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_up, stream));
     ctx->mel_used = true;                                      // (from here on the staging and the table are in use)
-    if (!is_c) {
+    if (clx_mel_is_f(spec->t)) {
+        hipLaunchKernelGGL(clx_k_mel_f, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                           (const uint32_t*)ctx->d_mel, spec->dev, clx_mel_fargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
+    } else if (!is_c) {
         hipLaunchKernelGGL(clx_k_mel, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
                            (const uint32_t*)ctx->d_mel, spec->dev, n_groups, window_len, n_frames, layout, (float*)d_out);
     } else {

@@ -40,7 +40,19 @@
 // clx_k_mel_range then clamps every cell of window k to wmax[k] - D and applies the affine, in place, behind it on the same stream:
 // pure streaming, 16-byte accesses on the window's 16-byte grid, the ragged head and tail vectors float by float.
 //
-// clx_mel_build / clx_mel_check / clx_mel_fill / clx_mel_fill_c are the host side (plain C++, shared with the wave simulator).
+// clx_k_mel_f is the third instantiation: a framed spec that conditions each frame before the window (claxon_hip.h,
+// clx_mel_create_framed), which is Kaldi's fbank.  Frames overlap, so the conditioning cannot be done once on the
+// batch; it happens where a frame's slice is staged.  A prologue gives the block's live frames their sums: 8 lanes per frame, lane i
+// of the 8 adds the frame's samples i, i + 8, ... in ascending order, three shuffles fold the 8 partial sums (xor 4, 2, 1), the
+// mean is one correctly rounded division.  The 32 means cross the block through the first 32 words of the staging area, which
+// nothing else uses yet, and stay in two registers of the lane that stages the frames they belong to: LDS stays 35 072 bytes.  The
+// staged value is then y[n], from a[.. + n], a[.. + n - 1] (a[.. + n] itself at n = 0) and the frame's mean -- two more loads per
+// lane and slice, of floats the neighbouring lane loads anyway, and three rounded operations.  A frame shorter than the transform,
+// a bank that stops below the Nyquist bin and the whole-frame rule need no kernel of their own: the table has rows (slices) for
+// win_length taps and passes for n_bins bins only, and clx_k_mel runs a framed spec that does not condition.
+//
+// clx_mel_build / clx_mel_build_framed / clx_mel_check / clx_mel_fill / clx_mel_fill_c are the host side (plain C++, shared with the
+// wave simulator).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
@@ -56,8 +68,15 @@ struct clx_mel_dev {
     const float* basis;      // [n_pad][n_pass][2][256]: cos then sin of the pass's 256 bins, zero padded
     const float* fbank;      // [n_mels][J]
     const uint32_t* ends;    // [n_mels][2]: a row's first non-zero bin and one past its last (equal: an all-zero row)
-    uint32_t n_fft, hop, n_mels, n_bins, n_pass, n_slices, mode;
+    uint32_t n_fft, hop, n_mels, n_bins, n_pass, n_slices, mode;   // (n_fft: the taps of a frame, win_length of a framed spec)
     float floor;
+};
+
+// what clx_k_mel_f needs on top of it (passed by value, uniform): whether the frame's mean is removed, and the pre-emphasis
+// coefficient (0: none)
+struct clx_mel_fdev {
+    uint32_t remove_dc;
+    float preemph;
 };
 
 // what clx_k_mel_c needs on top of it (passed by value): P = n_fft / 2 of a centred spec (else 0), zero = 1 for CLX_MEL_PAD_ZERO
@@ -72,6 +91,8 @@ struct clx_mel_tables {
     float floor = 0.f;
     uint32_t center = 0, pad = 0, range = 0;                 // clx_mel_opts (all zero: the plain spec)
     float range_width = 0.f, shift = 0.f, scale = 0.f;
+    uint32_t win = 0, remove_dc = 0, whole = 0;              // clx_mel_create_framed: win_length (else n_fft) and clx_mel_frame_opts
+    float preemph = 0.f;
     std::vector<float> basis, fbank;
     std::vector<uint32_t> ends;
 };
@@ -83,6 +104,7 @@ constexpr uint32_t kStage = kKS * kRow + kKS * kXsRow;          // floats of the
 constexpr uint32_t kLdsBytes = kStage * 4u;                     // 35 072
 constexpr uint32_t kRangeVecs = 1024u;                          // 16-byte vectors of a clx_k_mel_range block: 4 per lane
 static_assert(kF * kPRow <= kStage, "P fits in the staging area");
+static_assert(kThreads == 8u * kF, "the prologue of clx_k_mel_f sums a frame with 8 lanes");
 static_assert(2u * kLdsBytes <= 160u * 1024u, "two workgroups share a CU's LDS");
 
 // four floats moved as one 16-byte value (a vector type, so that a copy is a load and a store and never a memcpy through a stack slot)
@@ -106,17 +128,30 @@ __device__ __forceinline__ uint32_t enc(float v) { const uint32_t b = bits_of(v)
 __device__ __forceinline__ float dec(uint32_t e) { return float_of((e & 0x80000000u) ? e ^ 0x80000000u : ~e); }
 constexpr uint32_t kEncNegInf = 0x007fffffu;                    // enc(-inf): what the host puts into wmax[k] before the launch
 
-// a subtract, an add and a multiply that are each rounded once and never contracted (the wave simulator's host build is compiled
+// a subtract, an add, a multiply and a divide that are each rounded once and never contracted (the wave simulator's host build is compiled
 // without contraction)
 #if defined(__HIP__) || defined(__HIPCC__)
 __device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
 #else
 inline float sub_rn(float a, float b) { return a - b; }
 inline float add_rn(float a, float b) { return a + b; }
 inline float mul_rn(float a, float b) { return a * b; }
+inline float div_rn(float a, float b) { return a / b; }
 #endif
+
+// d - c * p with the product and the difference each rounded once.  __fmul_rn and __fsub_rn are a plain * and - to hipcc, and a
+// product that feeds a difference is contracted into one fma unless the two operations themselves are compiled with contraction
+// off, which is what this function is for (the steps of clx_k_mel_range are a sum feeding a product: nothing to contract).
+__device__ __forceinline__ float msub_rn(float d, float c, float p) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float m = c * p;
+    return d - m;
+}
 
 // The index map of a centred frame: tap i = t * H + n - P of the window p[] that continues a[0 .. L) on both sides -- by reflection
 // about 0 and L - 1, or (zero) by zeros.  Only a float of [0, lim) is loaded: lim = L in reflect mode (clx_mel_check's conditions
@@ -136,12 +171,12 @@ __device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mel
 
 // Block b: frame group b % n_groups of window b / n_groups (clx_mel_check gives n_groups).  `audio` is [B, L], vframes[k] =
 // valid_frames[k] <= n_frames, `out` is [B, n_mels, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_mels] (CLX_WINDOW_TC).  kC: the
-// centred and/or ranged form (X, lim[k] and wmax[k] are used by it alone).
+// centred and/or ranged form (X, lim[k] and wmax[k] are used by it alone).  kFr: the conditioning form (F is used by it alone).
 namespace clx_mel {
-template <bool kC>
+template <bool kC, bool kFr>
 __device__ __forceinline__ void body(const float* __restrict__ audio, const uint32_t* __restrict__ vframes,
-                                     const clx_mel_dev S, const clx_mel_cdev X, const uint32_t* __restrict__ lim, uint32_t* wmax,
-                                     uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout, float* __restrict__ out) {
+                                     const clx_mel_dev S, const clx_mel_cdev X, const clx_mel_fdev F, const uint32_t* __restrict__ lim,
+                                     uint32_t* wmax, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout, float* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float s_stage[kStage];
     const uint32_t tid = threadIdx.x, k = blockIdx.x / n_groups, f0 = (blockIdx.x - k * n_groups) * kF;
     const uint32_t vf = vframes[k];
@@ -177,6 +212,29 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
         i1 = i0 + (int64_t)(16ull * S.hop);
         lm = lim[k];
     }
+    // kFr: the means of this lane's two frames (0 when the mean stays), and the frames' first samples
+    float mu0 = 0.f, mu1 = 0.f;
+    const float* a0 = a;
+    const float* a1 = a;
+    if constexpr (kFr) {
+        a0 = a + (uint64_t)(f0 + x_f) * S.hop;
+        a1 = a + (uint64_t)(f0 + x_f + 16u) * S.hop;
+        if (F.remove_dc) {                                     // (uniform over the block)
+            const uint32_t sf = tid >> 3;                      // lanes 8 sf .. 8 sf + 7 sum frame sf
+            float sum = 0.f;
+            if (sf < nf_live) {
+                const float* const fr = a + (uint64_t)(f0 + sf) * S.hop;
+                for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) sum = add_rn(sum, fr[n]);
+            }
+            sum = add_rn(sum, __shfl_xor(sum, 4));
+            sum = add_rn(sum, __shfl_xor(sum, 2));
+            sum = add_rn(sum, __shfl_xor(sum, 1));
+            if ((tid & 7u) == 0u) s_stage[sf] = div_rn(sum, (float)S.n_fft);
+            __syncthreads();
+            mu0 = s_stage[x_f];
+            mu1 = s_stage[x_f + 16u];                          // (read before the first round's barrier, behind which the staging begins)
+        }
+    }
 
     for (uint32_t p = 0; p < S.n_pass; ++p) {
         const bool lane_live = wave_live && p * kBins + 4u * q < S.n_bins;
@@ -190,6 +248,7 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
         for (uint32_t s = 0; s <= S.n_slices; ++s) {
             f4 pb0, pb1, pb2, pb3, pb4, pb5, pb6, pb7;
             float px0 = 0.f, px1 = 0.f;
+            float pv0 = 0.f, pv1 = 0.f;                        // kFr with pre-emphasis: the samples in front of px0 and px1
             if (s < S.n_slices) {
                 const float* const r = bp + ((uint64_t)s * kKS + b_row) * row_stride;
                 pb0 = *reinterpret_cast<const f4*>(r);
@@ -205,6 +264,10 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
                     if constexpr (kC) {
                         if (x_f < nf_live) px0 = tap(a, i0 + (int64_t)(s * kKS), L, lm, X.zero);
                         if (x_f + 16u < nf_live) px1 = tap(a, i1 + (int64_t)(s * kKS), L, lm, X.zero);
+                    } else if constexpr (kFr) {
+                        const uint32_t nb = n ? n - 1u : 0u;   // (the first tap refers to the frame's own first sample)
+                        if (x_f < nf_live) { px0 = a0[n]; if (F.preemph > 0.f) pv0 = a0[nb]; }
+                        if (x_f + 16u < nf_live) { px1 = a1[n]; if (F.preemph > 0.f) pv1 = a1[nb]; }
                     } else {
                         if (x_f < nf_live) px0 = a[(uint64_t)(f0 + x_f) * S.hop + n];
                         if (x_f + 16u < nf_live) px1 = a[(uint64_t)(f0 + x_f + 16u) * S.hop + n];
@@ -240,6 +303,16 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
                 *reinterpret_cast<f4*>(d + 10u * kRow) = pb5;
                 *reinterpret_cast<f4*>(d + 12u * kRow) = pb6;
                 *reinterpret_cast<f4*>(d + 14u * kRow) = pb7;
+                if constexpr (kFr) {                           // d = x - mu, y = d - c * d', each step rounded once (a dead frame: 0)
+                    if (s * kKS + x_kk < S.n_fft) {            // (a tap past the frame stays +0.0)
+                        if (F.remove_dc) { px0 = sub_rn(px0, mu0); px1 = sub_rn(px1, mu1); }
+                        if (F.preemph > 0.f) {
+                            if (F.remove_dc) { pv0 = sub_rn(pv0, mu0); pv1 = sub_rn(pv1, mu1); }
+                            px0 = msub_rn(px0, F.preemph, pv0);
+                            px1 = msub_rn(px1, F.preemph, pv1);
+                        }
+                    }
+                }
                 xs[x_kk * kXsRow + x_f] = px0;
                 xs[x_kk * kXsRow + x_f + 16u] = px1;
             }
@@ -307,7 +380,14 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
 extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
                                                             uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
                                                             float* __restrict__ out) {
-    clx_mel::body<false>(audio, vframes, S, clx_mel_cdev(), nullptr, nullptr, n_groups, L, n_frames, layout, out);
+    clx_mel::body<false, false>(audio, vframes, S, clx_mel_cdev(), clx_mel_fdev(), nullptr, nullptr, n_groups, L, n_frames, layout, out);
+}
+
+// The conditioning form of a framed spec (remove_dc and / or preemph > 0); otherwise clx_k_mel's arguments.
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel_f(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
+                                                              clx_mel_fdev F, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
+                                                              float* __restrict__ out) {
+    clx_mel::body<false, true>(audio, vframes, S, clx_mel_cdev(), F, nullptr, nullptr, n_groups, L, n_frames, layout, out);
 }
 
 // The centred and/or ranged form.  `table` is the call's device table: vframes[B], then lim[B] (the end of what a tap may load of
@@ -316,7 +396,7 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restr
 extern "C" __global__ __launch_bounds__(256) void clx_k_mel_c(const float* __restrict__ audio, uint32_t* table, uint32_t n_windows, clx_mel_dev S,
                                                               clx_mel_cdev X, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
                                                               float* __restrict__ out) {
-    clx_mel::body<true>(audio, table, S, X, table + n_windows, table + 2u * (uint64_t)n_windows, n_groups, L, n_frames, layout, out);
+    clx_mel::body<true, false>(audio, table, S, X, clx_mel_fdev(), table + n_windows, table + 2u * (uint64_t)n_windows, n_groups, L, n_frames, layout, out);
 }
 
 // The range step, in place: out[k][c] = fl32(fl32(max(out[k][c], fl32(max_k - D)) + shift) * scale) for the `cells` cells of window
@@ -352,10 +432,16 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel_range(float* out, co
 
 // The host side of clx_mel_create: checks the spec's arguments (empty: fine, else the text for clx_last_error) and builds its
 // tables: the basis in double, rounded once, in the padded layout the kernel stages from; a copy of the filterbank; each row's ends.
-// `opts` (clx_mel_create_ex; nullptr: all zero) is checked and copied into the tables.
-inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels, uint32_t mode,
-                                 float floor, clx_mel_tables* t, const clx_mel_opts* opts = nullptr) {
+// `opts` (clx_mel_create_ex; nullptr: all zero) is checked and copied into the tables.  The framed form (clx_mel_create_framed) has a
+// window of win_length <= n_fft taps -- the table gets rows for those taps only, the angle stays over n_fft -- and a filterbank over
+// the first n_bins bins -- the table gets passes for those only; `fopts` (nullptr: all zero) is checked and copied likewise.  With
+// win_length == n_fft and n_bins == n_fft / 2 + 1 the tables are clx_mel_create's.
+inline std::string clx_mel_build_framed(uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank, uint32_t n_bins,
+                                        uint32_t n_mels, uint32_t mode, float floor, clx_mel_tables* t, const clx_mel_opts* opts,
+                                        const clx_mel_frame_opts* fopts) {
     if (n_fft < 2u || n_fft > 2048u) return "clx_mel_create: n_fft must be 2..2048";
+    if (win_length < 1u || win_length > n_fft) return "clx_mel_create_framed: win_length must be 1..n_fft";
+    if (n_bins < 1u || n_bins > n_fft / 2u + 1u) return "clx_mel_create_framed: n_bins must be 1..n_fft / 2 + 1";
     if (hop < 1u) return "clx_mel_create: hop must be at least 1";
     if (n_mels < 1u || n_mels > clx_mel::kMaxMels) return "clx_mel_create: n_mels must be 1..256";
     if (mode != CLX_MEL_POWER && mode != CLX_MEL_LN && mode != CLX_MEL_LOG10) return "clx_mel_create: mode must be CLX_MEL_POWER, CLX_MEL_LN or CLX_MEL_LOG10";
@@ -374,15 +460,21 @@ inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* wind
         t->center = opts->center; t->pad = opts->pad; t->range = opts->range;
         t->range_width = opts->range_width; t->shift = opts->shift; t->scale = opts->scale;
     }
+    if (fopts) {
+        if (fopts->remove_dc > 1u) return "clx_mel_create_framed: remove_dc must be 0 or 1";
+        if (fopts->whole_frames > 1u) return "clx_mel_create_framed: whole_frames must be 0 or 1";
+        if (!std::isfinite(fopts->preemph) || !(fopts->preemph >= 0.f) || !(fopts->preemph <= 1.f)) return "clx_mel_create_framed: preemph must be finite and in 0..1";
+        t->remove_dc = fopts->remove_dc; t->whole = fopts->whole_frames; t->preemph = fopts->preemph > 0.f ? fopts->preemph : 0.f;
+    }
     using namespace clx_mel;
-    const uint32_t N = n_fft, J = N / 2u + 1u;
-    t->n_fft = N; t->hop = hop; t->n_mels = n_mels; t->n_bins = J; t->mode = mode; t->floor = floor;
+    const uint32_t N = n_fft, Nw = win_length, J = n_bins;
+    t->n_fft = N; t->win = Nw; t->hop = hop; t->n_mels = n_mels; t->n_bins = J; t->mode = mode; t->floor = floor;
     t->n_pass = (J + kBins - 1u) / kBins;
-    t->n_slices = (N + kKS - 1u) / kKS;
+    t->n_slices = (Nw + kKS - 1u) / kKS;
     const size_t row = (size_t)t->n_pass * kRow;
     t->basis.assign((size_t)t->n_slices * kKS * row, 0.f);
     const double two_pi = 2.0 * 3.14159265358979323846;
-    for (uint32_t n = 0; n < N; ++n)
+    for (uint32_t n = 0; n < Nw; ++n)
         for (uint32_t j = 0; j < J; ++j) {
             const double ang = two_pi * (double)(((uint64_t)j * n) % N) / (double)N;     // (in this order: 2 pi k, then / N)
             float* const at = t->basis.data() + (size_t)n * row + (size_t)(j / kBins) * kRow + j % kBins;
@@ -401,9 +493,15 @@ inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* wind
     return std::string();
 }
 
+inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels, uint32_t mode,
+                                 float floor, clx_mel_tables* t, const clx_mel_opts* opts = nullptr) {
+    return clx_mel_build_framed(n_fft, n_fft, hop, window, fbank, n_fft / 2u + 1u, n_mels, mode, floor, t, opts, nullptr);
+}
+
 // The host side of clx_mel_windows: checks the arguments (nullptr: fine, else the text for clx_last_error) and gives the launch
 // shape: *n_groups frame groups per window (0: nothing to launch), n_windows * *n_groups blocks of clx_mel::kThreads.  A centred
-// spec is held to torch.stft's frame count (P = n_fft / 2 < window_len, and the last frame ends inside window_len + 2 P); a ranged
+// spec is held to torch.stft's frame count (P = n_fft / 2 < window_len, and the last frame ends inside window_len + 2 P), any other
+// to (n_frames - 1) * hop + win_length <= window_len (win_length = n_fft unless the spec is framed); a ranged
 // one also gets *n_tiles, the tiles per window of clx_k_mel_range (n_windows * *n_tiles blocks).
 inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, size_t n_windows, uint32_t window_len, const uint32_t* valid,
                                  uint32_t n_frames, uint32_t layout, const void* out, uint32_t* n_groups, uint32_t* n_tiles = nullptr) {
@@ -417,7 +515,9 @@ inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, siz
         const uint64_t P = t->n_fft / 2u;
         if (P >= window_len) return "clx_mel_windows: a centred spec needs n_fft / 2 less than window_len";
         if ((uint64_t)window_len + 2u * P < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len + 2 * (n_fft / 2) is less than (n_frames - 1) * hop + n_fft";
-    } else if ((uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len is less than (n_frames - 1) * hop + n_fft";
+    } else if ((uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->win)
+        return t->win == t->n_fft ? "clx_mel_windows: window_len is less than (n_frames - 1) * hop + n_fft"
+                                  : "clx_mel_windows: window_len is less than (n_frames - 1) * hop + win_length";
     for (size_t k = 0; k < n_windows; ++k)
         if (valid[k] > window_len) return "clx_mel_windows: valid[k] is larger than window_len";
     const uint64_t groups = ((uint64_t)n_frames + clx_mel::kF - 1u) / clx_mel::kF;
@@ -432,12 +532,28 @@ inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, siz
 }
 
 // valid_frames[k] = clamp(ceil(valid[k] / hop), 0, n_frames); centred by P: 0 for valid[k] == 0, else min(n_frames,
-// ceil((valid[k] + P) / hop)), the frames with t * hop - P < valid[k]
-inline void clx_mel_fill(uint32_t* vframes, const uint32_t* valid, size_t n_windows, uint32_t hop, uint32_t n_frames, uint32_t P = 0u) {
+// ceil((valid[k] + P) / hop)), the frames with t * hop - P < valid[k].  whole_win (a framed spec that counts whole frames only: its
+// win_length; else 0): 0 for valid[k] < whole_win, else min(n_frames, 1 + (valid[k] - whole_win) / hop)
+inline void clx_mel_fill(uint32_t* vframes, const uint32_t* valid, size_t n_windows, uint32_t hop, uint32_t n_frames, uint32_t P = 0u,
+                         uint32_t whole_win = 0u) {
     for (size_t k = 0; k < n_windows; ++k) {
-        const uint64_t v = valid[k] ? ((uint64_t)valid[k] + P + hop - 1u) / hop : 0u;
+        uint64_t v;
+        if (whole_win) v = valid[k] < whole_win ? 0u : 1u + (uint64_t)(valid[k] - whole_win) / hop;
+        else v = valid[k] ? ((uint64_t)valid[k] + P + hop - 1u) / hop : 0u;
         vframes[k] = v < n_frames ? (uint32_t)v : n_frames;
     }
+}
+
+// (clx_mel_fill's whole_win of a spec)
+inline uint32_t clx_mel_whole(const clx_mel_tables& t) { return t.whole ? t.win : 0u; }
+
+// clx_k_mel_f runs a spec that conditions its frames
+inline bool clx_mel_is_f(const clx_mel_tables& t) { return t.remove_dc != 0u || t.preemph > 0.f; }
+
+inline clx_mel_fdev clx_mel_fargs(const clx_mel_tables& t) {
+    clx_mel_fdev f;
+    f.remove_dc = t.remove_dc; f.preemph = t.preemph;
+    return f;
 }
 
 inline bool clx_mel_is_c(const clx_mel_tables& t) { return t.center != 0u || t.range != 0u; }
@@ -462,7 +578,7 @@ inline void clx_mel_fill_c(uint32_t* table, const uint32_t* valid, size_t n_wind
 inline clx_mel_dev clx_mel_args(const clx_mel_tables& t, const float* basis, const float* fbank, const uint32_t* ends) {
     clx_mel_dev d;
     d.basis = basis; d.fbank = fbank; d.ends = ends;
-    d.n_fft = t.n_fft; d.hop = t.hop; d.n_mels = t.n_mels; d.n_bins = t.n_bins; d.n_pass = t.n_pass; d.n_slices = t.n_slices; d.mode = t.mode;
+    d.n_fft = t.win; d.hop = t.hop; d.n_mels = t.n_mels; d.n_bins = t.n_bins; d.n_pass = t.n_pass; d.n_slices = t.n_slices; d.mode = t.mode;
     d.floor = t.floor;
     return d;
 }

@@ -512,6 +512,43 @@ enum { CLX_MEL_PAD_REFLECT = 0, CLX_MEL_PAD_ZERO = 1 };
 typedef struct { uint32_t center, pad, range; float range_width, shift, scale; } clx_mel_opts;
 int  clx_mel_create_ex(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels,
                        uint32_t mode, float floor, const clx_mel_opts* opts, clx_mel_spec** spec);
+/* Framed specs: a frame shorter than the transform, conditioned before the window, over the first n_bins bins, counted in whole
+ * frames (clx_k_mel_f).  This is what Kaldi's fbank needs (torchaudio.compliance.kaldi.fbank, kaldi-native-fbank):
+ * 400 samples padded at the end to 512, each frame's own mean removed and a pre-emphasis applied whose first tap refers to the
+ * frame's own first sample, 256 of 257 bins, snip_edges.  The spec is (n_fft N in 2..2048, win_length Nw in 1..N, a float32 window
+ * w[Nw], n_bins in 1..N/2+1, a float32 filterbank fb[n_mels][n_bins], and hop, n_mels, mode, floor as clx_mel_create), with
+ * opts == NULL meaning all zero: remove_dc and whole_frames are 0 or 1, preemph is finite and in [0, 1], 0 meaning none.  The handle
+ * is an ordinary clx_mel_spec for clx_mel_windows and clx_mel_destroy.  A framed spec is uncentred and unranged.
+ *
+ *   frame      frame t of window k is x[n] = a[k][t*H + n], n = 0..Nw-1.  clx_mel_windows requires (n_frames-1)*H + Nw <= L.
+ *   conditioning  All in float32, each operation rounded once, none contracted.  If remove_dc: S = sum_n x[n] in the kernel's
+ *              order (8 partial sums over n = i, i+8, .. ascending, folded pairwise), mu = fl32(S / (float)Nw) and
+ *              d[n] = fl32(x[n] - mu); otherwise d = x.  If preemph = c > 0: y[n] = fl32(d[n] - fl32(c d[n-1])) for n >= 1 and
+ *              y[0] = fl32(d[0] - fl32(c d[0])) -- Kaldi's in-place loop; otherwise y = d.
+ *   basis      c[j][n] = fl32(w[n] cos(2 pi ((j n) mod N) / N)), s[j][n] = fl32(-w[n] sin(..)) for j < n_bins and n < Nw, built in
+ *              double and rounded once as for clx_mel_create.  A tap n >= Nw does not exist (the padding to N is zeros and is
+ *              not multiplied).
+ *   the rest   re_j, im_j, P_j, M_m and the mode are clx_mel_create's with y in place of x and n_bins in place of J.  A
+ *              filterbank row may be all zero (with many bands Kaldi's lowest ones are): it gives finish(0), i.e. 0, logf(floor)
+ *              or log10f(floor).
+ *   bound      For ANY order of the sums, with mean|x| = sum_n |x[n]| / Nw, x[n'] the sample in front of x[n] (x[0] for n = 0)
+ *              and y* the exact conditioning of the float32 samples:  dmu = g(Nw+1) mean|x|;
+ *              dy[n] = (1+c) dmu + g(3)(|x[n]| + c|x[n']| + (1+c)(|mu| + dmu));
+ *              dre_j = g(Nw+2) sum_n (|y*[n]| + dy[n]) |c[j][n]| + sum_n dy[n] |c[j][n]|, dim_j likewise; from dre and dim to dM
+ *              as for clx_mel_create.  Without remove_dc the dmu and mu terms drop, without pre-emphasis the c terms.
+ *   validity   whole_frames = 0: valid_frames[k] = clamp(ceil(valid[k] / H), 0, n_frames) as ever.  whole_frames = 1:
+ *              valid_frames[k] = valid[k] < Nw ? 0 : min(n_frames, 1 + (valid[k] - Nw) / H), Kaldi's snip_edges count: a
+ *              half-empty frame with its mean removed is not silence.  A dead frame is +0.0 and is not computed; no float
+ *              outside a live frame is read.
+ *
+ * With remove_dc == 0 and preemph == 0 the launch is clx_k_mel on the spec's tables, and with Nw == N and n_bins == N/2+1 as well
+ * the tables are clx_mel_create's, word for word.  CLX_API_ERROR for clx_mel_create's refusals and for a win_length outside 1..n_fft,
+ * n_bins outside 1..n_fft/2+1, remove_dc or whole_frames other than 0 or 1, and a preemph that is not finite or not in [0, 1].
+ * The definition restates Kaldi's; it has not been compared with a Kaldi binary. */
+typedef struct { uint32_t remove_dc, whole_frames; float preemph; } clx_mel_frame_opts;
+int  clx_mel_create_framed(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window /*[win_length]*/,
+                           const float* fbank /*[n_mels][n_bins]*/, uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor,
+                           const clx_mel_frame_opts* opts, clx_mel_spec** spec);
 void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
 /* The features of d_audio [n_windows][window_len] (device, float32) into d_out (device, float32), asynchronously on `stream`
  * (NULL: the context's).  valid is a host array; it is staged like the window table of clx_gather_windows: pinned staging, a
@@ -520,7 +557,8 @@ void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
  * another context, window_len < (n_frames-1)*hop + n_fft, a valid[k] > window_len and an unknown layout.  n_windows == 0 or
  * n_frames == 0 succeeds and launches nothing.  The spec decides the kernel, the length condition and the valid_frames rule: a
  * centred or ranged spec runs clx_k_mel_c (its table also carries, per window, the end of what may be loaded and the encoded
- * maximum, initialised by the upload), a ranged one clx_k_mel_range behind it. */
+ * maximum, initialised by the upload), a ranged one clx_k_mel_range behind it; a framed spec is held to win_length in place of
+ * n_fft and to its own valid_frames rule, and runs clx_k_mel_f if it conditions its frames. */
 int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
                      const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
