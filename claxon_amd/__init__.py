@@ -101,7 +101,7 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
-    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_destroy", "clx_mel_windows",
+    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_destroy", "clx_mel_windows",
 ]
 
 
@@ -187,6 +187,8 @@ def lib():
     L.clx_mel_create_ex.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, vp, C.POINTER(vp)]
     L.clx_mel_create_framed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
                                         C.POINTER(vp)]
+    L.clx_mel_create_cepstral.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
+                                          vp, C.POINTER(vp)]
     L.clx_mel_destroy.argtypes = [vp, vp]
     L.clx_mel_destroy.restype = None
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
@@ -714,8 +716,8 @@ class Context:
 
     def mel_windows(self, spec, audio, valid, n_frames, layout, out, stream=None):
         """clx_mel_windows: the features of `spec` (a MelSpec of this context) for the dense mono batch `audio` [B, L] (float32, the
-        samples from valid[k] on zero), n_frames frames per window, written to `out` as [B, n_frames, n_mels] (WINDOW_TC) or
-        [B, n_mels, n_frames] (WINDOW_CT); a frame from spec.valid_frames(valid[k], n_frames) on is zeros (the scaled silence value
+        samples from valid[k] on zero), n_frames frames per window, written to `out` as [B, n_frames, n_out] (WINDOW_TC) or
+        [B, n_out, n_frames] (WINDOW_CT), n_out = spec.n_out: n_mels, or n_ceps of a cepstral spec; a frame from spec.valid_frames(valid[k], n_frames) on is zeros (the scaled silence value
         for a spec with top).  A centred spec takes the [B, L] batch as the crops its frames are centred on.  `audio` and `out` are CUDA float32 tensors
         (B and L are the tensor's) or `audio` is a (pointer, B, L) triple and `out` a pointer.  Asynchronous on `stream` as
         gather_windows is."""
@@ -1258,6 +1260,11 @@ class _MelFrameOpts(C.Structure):        # clx_mel_frame_opts
     _fields_ = [("remove_dc", C.c_uint32), ("whole_frames", C.c_uint32), ("preemph", C.c_float)]
 
 
+class _MelCepOpts(C.Structure):          # clx_mel_cep_opts
+    _fields_ = [("n_ceps", C.c_uint32), ("dct", C.c_void_p), ("lifter", C.c_void_p), ("energy", C.c_uint32), ("energy_scale", C.c_float),
+                ("energy_floor", C.c_float)]
+
+
 def _hz_to_mel(f, scale):
     f = np.asarray(f, dtype=np.float64)
     if scale == "htk":
@@ -1359,6 +1366,30 @@ def mel_fbank_kaldi(sample_rate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
     return np.ascontiguousarray(fb.astype(np.float32))
 
 
+def mel_dct(n_ceps, n_mels):
+    """Kaldi's ComputeDctMatrix [n_ceps, n_mels] (float32, built in double and rounded once): the first n_ceps rows of the
+    orthonormal DCT-II -- row 0 is sqrt(1 / n_mels), row k is sqrt(2 / n_mels) cos(pi / n_mels (m + 0.5) k)."""
+    n_ceps, n_mels = int(n_ceps), int(n_mels)
+    if not 1 <= n_ceps <= n_mels:
+        raise ValueError("mel_dct: need 1 <= n_ceps <= n_mels, not %d and %d" % (n_ceps, n_mels))
+    k = np.arange(n_ceps, dtype=np.float64)[:, None]
+    m = np.arange(n_mels, dtype=np.float64)[None, :]
+    d = math.sqrt(2.0 / n_mels) * np.cos((math.pi / n_mels) * (m + 0.5) * k)
+    d[0, :] = math.sqrt(1.0 / n_mels)
+    return np.ascontiguousarray(d.astype(np.float32))
+
+
+def mel_lifter_kaldi(n_ceps, Q=22.0):
+    """Kaldi's cepstral lifter [n_ceps] (float32, built in double and rounded once): 1 + 0.5 Q sin(pi i / Q).  Q = 0: None, no
+    lifter."""
+    n_ceps, Q = int(n_ceps), float(Q)
+    if n_ceps < 1 or not math.isfinite(Q) or Q < 0:
+        raise ValueError("mel_lifter_kaldi: need n_ceps >= 1 and a finite Q >= 0, not %d and %r" % (n_ceps, Q))
+    if Q == 0.0:
+        return None
+    return (1.0 + 0.5 * Q * np.sin(math.pi * np.arange(n_ceps, dtype=np.float64) / Q)).astype(np.float32)
+
+
 class MelSpec:
     """A feature spec for Context.mel_windows and StreamSet.read_mel (clx_mel_create, claxon_hip.h): frames of n_fft samples every
     `hop`, the periodic Hann window (.window), a triangular mel filterbank (.fbank, [n_mels, n_fft // 2 + 1]: mel_fbank) and the last
@@ -1375,7 +1406,15 @@ class MelSpec:
 
     MelSpec.framed() builds a spec from a window and a filterbank of the caller's, with a frame shorter than the transform, each
     frame's mean removed and pre-emphasised before the window, a bank over the first bins only and whole frames counted
-    (clx_mel_create_framed); MelSpec.kaldi() is Kaldi's fbank that way."""
+    (clx_mel_create_framed); MelSpec.kaldi() is Kaldi's fbank that way.  With a DCT, MelSpec.framed() builds a cepstral spec
+    (clx_mel_create_cepstral): n_ceps rows of cepstra, liftered, with the frame's log energy in row 0 if asked for; MelSpec.mfcc()
+    is Kaldi's MFCC that way.  n_out is the rows of a spec's output: n_ceps of a cepstral spec, n_mels of any other."""
+
+    n_ceps, dct, lifter, energy, energy_scale, energy_floor = None, None, None, False, 1.0, 0.0    # (not cepstral unless framed() says so)
+
+    @property
+    def n_out(self):
+        return self.n_mels if self.n_ceps is None else self.n_ceps
 
     def __init__(self, ctx, sample_rate, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, mode="ln",
                  floor=1e-10, center=False, pad_mode="reflect", top=None, shift=0.0, scale=1.0):
@@ -1433,12 +1472,18 @@ class MelSpec:
 
     @classmethod
     def framed(cls, ctx, sample_rate, n_fft, win_length, hop, window, fbank, mode="ln", floor=1e-10, remove_dc=False, preemph=0.0,
-               whole_frames=False):
+               whole_frames=False, dct=None, lifter=None, energy=False, energy_scale=1.0, energy_floor=0.0):
         """The general framed spec (clx_mel_create_framed, claxon_hip.h): frames of win_length <= n_fft samples every `hop`, each
         with its own mean removed (remove_dc) and pre-emphasised by `preemph` (0: none; the first tap refers to the frame's own first
         sample), then `window` [win_length] and an n_fft-point transform of which the first n_bins bins go through `fbank`
         [n_mels, n_bins], n_bins <= n_fft // 2 + 1; rows of the bank may be all zero.  whole_frames counts only frames that lie
-        inside a window's valid samples.  The tables are taken as float32.  ctx=None keeps the tables only."""
+        inside a window's valid samples.  The tables are taken as float32.  ctx=None keeps the tables only.
+
+        With `dct` [n_ceps, n_mels] the spec is cepstral (clx_mel_create_cepstral): row i of the output is dct[i] . (the frame's
+        n_mels cells), times lifter[i] if `lifter` [n_ceps] is given; with `energy` row 0 is instead the logarithm of
+        energy_scale times the frame's energy -- taken after the mean's removal and before pre-emphasis and the window, floored at
+        FLT_EPSILON -- and not less than ln(energy_floor) if that is greater than 0.  A cepstral spec has at most 128 bands and
+        256 bins.  Without `dct` the other four must be left alone."""
         for name, v in (("sample_rate", sample_rate), ("n_fft", n_fft), ("win_length", win_length), ("hop", hop)):
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v:
                 raise ValueError("MelSpec.framed: %s must be a whole number, not %r" % (name, v))
@@ -1466,7 +1511,36 @@ class MelSpec:
         if not (math.isfinite(self.preemph) and 0.0 <= self.preemph <= 1.0):
             raise ValueError("MelSpec.framed: preemph must be finite and in 0..1, not %r" % (preemph,))
         self.center, self.pad_mode, self.top, self.shift, self.scale = False, "reflect", None, 0.0, 1.0
-        if ctx is not None:
+        if dct is None:
+            if lifter is not None or energy is not False or energy_scale != 1.0 or energy_floor != 0.0:
+                raise ValueError("MelSpec.framed: lifter, energy, energy_scale and energy_floor need a dct")
+        else:
+            self.dct = np.ascontiguousarray(dct, dtype=np.float32)
+            if self.n_mels > 128 or self.n_bins > 256:
+                raise ValueError("MelSpec.framed: a cepstral spec has at most 128 bands and 256 bins, not %d and %d" % (self.n_mels, self.n_bins))
+            if self.dct.ndim != 2 or self.dct.shape[1] != self.n_mels or not 1 <= self.dct.shape[0] <= self.n_mels:
+                raise ValueError("MelSpec.framed: dct must be [n_ceps in 1..n_mels, n_mels = %d], not shape %r" % (self.n_mels, self.dct.shape))
+            self.n_ceps = int(self.dct.shape[0])
+            self.lifter = None if lifter is None else np.ascontiguousarray(lifter, dtype=np.float32)
+            if self.lifter is not None and self.lifter.shape != (self.n_ceps,):
+                raise ValueError("MelSpec.framed: lifter must have n_ceps = %d entries, not shape %r" % (self.n_ceps, self.lifter.shape))
+            if not isinstance(energy, (bool, np.bool_)):
+                raise ValueError("MelSpec.framed: energy must be True or False, not %r" % (energy,))
+            self.energy, self.energy_scale, self.energy_floor = bool(energy), float(np.float32(energy_scale)), float(np.float32(energy_floor))
+            if not (math.isfinite(self.energy_scale) and self.energy_scale > 0):
+                raise ValueError("MelSpec.framed: energy_scale must be finite and greater than 0, not %r" % (energy_scale,))
+            if not (math.isfinite(self.energy_floor) and self.energy_floor >= 0):
+                raise ValueError("MelSpec.framed: energy_floor must be finite and not negative, not %r" % (energy_floor,))
+        if ctx is not None and self.n_ceps is not None:
+            h = C.c_void_p(None)
+            opts = _MelFrameOpts(int(self.remove_dc), int(self.whole_frames), self.preemph)
+            cep = _MelCepOpts(self.n_ceps, _np_ptr(self.dct), None if self.lifter is None else _np_ptr(self.lifter), int(self.energy),
+                              self.energy_scale, self.energy_floor)
+            ctx._check(lib().clx_mel_create_cepstral(ctx._h, self.n_fft, self.win_length, self.hop, _np_ptr(self.window), _np_ptr(self.fbank),
+                                                     self.n_bins, self.n_mels, _MEL_MODES[mode], self.floor, C.byref(opts), C.byref(cep),
+                                                     C.byref(h)))
+            self._h = h
+        elif ctx is not None:
             h = C.c_void_p(None)
             opts = _MelFrameOpts(int(self.remove_dc), int(self.whole_frames), self.preemph)
             ctx._check(lib().clx_mel_create_framed(ctx._h, self.n_fft, self.win_length, self.hop, _np_ptr(self.window), _np_ptr(self.fbank),
@@ -1486,8 +1560,9 @@ class MelSpec:
         whole frames counted (snip_edges).  Kaldi works on samples in the int16 range: the window is multiplied by `scale` (32768)
         in double before its one rounding, and as the conditioning is linear a power-of-two scale gives what Kaldi gives on the
         int16-range input bit for bit.  read_mel(ids, starts, n_frames, MelSpec.kaldi(ctx)) is [B, n_mels, n_frames] ("tc":
-        Kaldi's own [n_frames, n_mels]).  dither, use_energy, snip_edges=False, vtln_warp and htk_compat are refused by name.  The
-        definition restates Kaldi's and has not been compared with a Kaldi binary."""
+        Kaldi's own [n_frames, n_mels]).  dither, use_energy, snip_edges=False, vtln_warp and htk_compat are refused by name (the
+        frame's energy is MelSpec.mfcc's use_energy; fbank's energy column is not provided).  The definition restates Kaldi's and
+        has not been compared with a Kaldi binary."""
         for name, v in refused.items():
             if name not in cls._KALDI_REFUSED:
                 raise TypeError("MelSpec.kaldi: unknown argument %r" % name)
@@ -1507,6 +1582,40 @@ class MelSpec:
         fbank = mel_fbank_kaldi(sample_rate, n_fft, n_mels, low_freq, high_freq)
         return cls.framed(ctx, sample_rate, n_fft, win_length, hop, window, fbank, mode="ln", floor=FLT_EPSILON, remove_dc=bool(remove_dc_offset),
                           preemph=preemphasis, whole_frames=True)
+
+    _MFCC_REFUSED = dict(dither=0.0, snip_edges=True, vtln_warp=1.0, htk_compat=False, raw_energy=True)
+
+    @classmethod
+    def mfcc(cls, ctx, sample_rate=16000, n_ceps=13, n_mels=23, cepstral_lifter=22.0, use_energy=False, energy_floor=0.0, frame_length_ms=25.0,
+             frame_shift_ms=10.0, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc_offset=True, window_type="povey", scale=32768.0,
+             **refused):
+        """Kaldi's MFCC (compute-mfcc-feats, torchaudio.compliance.kaldi.mfcc, lhotse's Mfcc) with torchaudio's defaults:
+        MelSpec.kaldi's frames, conditioning, window and n_mels = 23 bands by its rules, then the first n_ceps = 13 rows of the
+        orthonormal DCT-II of the log-mel cells (mel_dct) and the lifter 1 + 0.5 Q sin(pi i / Q) with Q = cepstral_lifter
+        (mel_lifter_kaldi; 0: none).  use_energy puts the frame's log energy in row 0 in place of C0 (Kaldi's raw_energy: before
+        pre-emphasis and the window), not less than ln(energy_floor) if that is greater than 0; the samples' int16-range scale enters
+        the energy as scale ** 2.  read_mel(ids, starts, n_frames, MelSpec.mfcc(ctx)) is [B, n_ceps, n_frames] ("tc": Kaldi's own
+        [n_frames, n_ceps]).  dither, snip_edges=False, vtln_warp, htk_compat and raw_energy=False are refused by name.  The
+        definition restates Kaldi's and has not been compared with a Kaldi binary."""
+        for name, v in refused.items():
+            if name not in cls._MFCC_REFUSED:
+                raise TypeError("MelSpec.mfcc: unknown argument %r" % name)
+            if isinstance(v, bool) != isinstance(cls._MFCC_REFUSED[name], bool) or v != cls._MFCC_REFUSED[name]:
+                raise ValueError("MelSpec.mfcc: %s=%r is not supported (only %r)" % (name, v, cls._MFCC_REFUSED[name]))
+        for name, v in (("n_ceps", n_ceps), ("n_mels", n_mels)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("MelSpec.mfcc: %s must be a whole number, not %r" % (name, v))
+        if not 1 <= int(n_mels) <= 128 or not 1 <= int(n_ceps) <= int(n_mels):
+            raise ValueError("MelSpec.mfcc: need n_mels in 1..128 and n_ceps in 1..n_mels, not %d and %d" % (n_mels, n_ceps))
+        if not isinstance(use_energy, (bool, np.bool_)):
+            raise ValueError("MelSpec.mfcc: use_energy must be True or False, not %r" % (use_energy,))
+        base = cls.kaldi(None, sample_rate=sample_rate, n_mels=int(n_mels), frame_length_ms=frame_length_ms, frame_shift_ms=frame_shift_ms,
+                         low_freq=low_freq, high_freq=high_freq, preemphasis=preemphasis, remove_dc_offset=remove_dc_offset,
+                         window_type=window_type, scale=scale)
+        return cls.framed(ctx, base.sample_rate, base.n_fft, base.win_length, base.hop, base.window, base.fbank, mode="ln", floor=FLT_EPSILON,
+                          remove_dc=base.remove_dc, preemph=base.preemph, whole_frames=True, dct=mel_dct(n_ceps, n_mels),
+                          lifter=mel_lifter_kaldi(n_ceps, cepstral_lifter), energy=bool(use_energy), energy_scale=float(scale) ** 2,
+                          energy_floor=energy_floor)
 
     def window_len(self, n_frames):
         """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame; win_length in place of n_fft for a
@@ -1759,8 +1868,8 @@ class StreamSet:
         one clx_mel_windows call on that [B, L] batch, with L = spec.window_len(n_frames): (n_frames - 1) * hop + n_fft, and for a
         centred spec `length` or n_frames * hop (the crop the frames are centred on and reflected at; it must be longer than
         n_fft // 2 and hold the frames: (n_frames - 1) * hop + n_fft <= length + 2 * (n_fft // 2)).  For an uncentred spec `length`
-        must be None or that L.  Returns (float32 tensor on the context's GPU: [B, n_mels, n_frames] for layout "ct",
-        [B, n_frames, n_mels] for "tc"; valid_frames): valid_frames[k] (int64 tensor) = spec.valid_frames(valid[k], n_frames) with
+        must be None or that L.  Returns (float32 tensor on the context's GPU: [B, n_out, n_frames] for layout "ct",
+        [B, n_frames, n_out] for "tc", n_out = spec.n_out: n_mels, or n_ceps of a cepstral spec; valid_frames): valid_frames[k] (int64 tensor) = spec.valid_frames(valid[k], n_frames) with
         valid[k] the window's samples inside its stream; a frame from there on is zeros, whatever the mode -- the scaled silence value
         for a spec with top.  The launches are queued behind read()'s, on the stream read() uses (gather_windows has the rule)."""
         import torch
@@ -1786,7 +1895,7 @@ class StreamSet:
                 raise ValueError("read_mel: length %d holds %d centred frames, not %d" % (L, 1 + (L + 2 * P - spec.n_fft) // spec.hop, n_frames))
         audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1)
         B = int(audio.shape[0])
-        out = torch.empty((B, spec.n_mels, n_frames) if layout == "ct" else (B, n_frames, spec.n_mels), dtype=torch.float32,
+        out = torch.empty((B, spec.n_out, n_frames) if layout == "ct" else (B, n_frames, spec.n_out), dtype=torch.float32,
                           device=audio.device)
         valid = valid.numpy()
         self.ctx.mel_windows(spec, audio.view(B, L), valid, n_frames, _LAYOUTS[layout], out)

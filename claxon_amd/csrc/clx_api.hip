@@ -277,8 +277,9 @@ struct clx_ctx {
 struct clx_mel_spec {
     clx_ctx* ctx = nullptr;
     clx_mel_tables t;
-    void* d_tables = nullptr;          // the basis, the filterbank and the rows' ends, in that order
+    void* d_tables = nullptr;          // the basis, the filterbank and the rows' ends, in that order (cepstral: then the DCT and the lifter)
     clx_mel_dev dev;
+    clx_mel_qdev qdev;                 // (a cepstral spec's)
 };
 
 // K2 build by batch size (groups of 64 predictor slots) unless CLX_K2_LATENCY / CLX_K2_THROUGHPUT force one
@@ -1573,27 +1574,32 @@ extern "C" int clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const 
     return clx_mel_create_ex(ctx, n_fft, hop, window, fbank, n_mels, mode, floor, nullptr, spec);
 }
 
-// clx_mel_create_ex and clx_mel_create_framed: the tables of either, uploaded
+// clx_mel_create_ex, clx_mel_create_framed and (cepstral) clx_mel_create_cepstral: the tables of any of them, uploaded
 static int clx_mel_create_any(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank,
                               uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_opts* opts,
-                              const clx_mel_frame_opts* fopts, clx_mel_spec** spec) {
+                              const clx_mel_frame_opts* fopts, clx_mel_spec** spec, bool cepstral = false, const clx_mel_cep_opts* qopts = nullptr) {
     if (!ctx) return CLX_API_ERROR;
     if (!spec) { ctx->last_error = "clx_mel_create: null argument"; return CLX_API_ERROR; }
     *spec = nullptr;
     clx_mel_spec* sp = new (std::nothrow) clx_mel_spec();
     if (!sp) { ctx->last_error = "clx_mel_create: out of memory"; return CLX_API_ERROR; }
-    const std::string why = clx_mel_build_framed(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, opts, fopts);
+    const std::string why = cepstral ? clx_mel_build_cepstral(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, fopts, qopts)
+                                     : clx_mel_build_framed(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, opts, fopts);
     if (!why.empty()) { delete sp; ctx->last_error = why; return CLX_API_ERROR; }
     sp->ctx = ctx;
     const size_t nb = sp->t.basis.size() * 4u, nf = (sp->t.fbank.size() * 4u + 15u) / 16u * 16u, ne = sp->t.ends.size() * 4u;
+    const size_t nd = sp->t.dct.size() * 4u, nl = sp->t.lifter.size() * 4u;
     bool ok = hip_ok(ctx, hipSetDevice(ctx->device), "hipSetDevice") &&
-              hip_ok(ctx, hipMalloc(&sp->d_tables, nb + nf + ne), "hipMalloc mel tables");
+              hip_ok(ctx, hipMalloc(&sp->d_tables, nb + nf + ne + nd + nl), "hipMalloc mel tables");
     char* d = (char*)sp->d_tables;
     ok = ok && hip_ok(ctx, hipMemcpy(d, sp->t.basis.data(), nb, hipMemcpyHostToDevice), "H2D mel basis") &&
          hip_ok(ctx, hipMemcpy(d + nb, sp->t.fbank.data(), sp->t.fbank.size() * 4u, hipMemcpyHostToDevice), "H2D mel filterbank") &&
          hip_ok(ctx, hipMemcpy(d + nb + nf, sp->t.ends.data(), ne, hipMemcpyHostToDevice), "H2D mel row ends");
+    if (nd) ok = ok && hip_ok(ctx, hipMemcpy(d + nb + nf + ne, sp->t.dct.data(), nd, hipMemcpyHostToDevice), "H2D mel dct");
+    if (nl) ok = ok && hip_ok(ctx, hipMemcpy(d + nb + nf + ne + nd, sp->t.lifter.data(), nl, hipMemcpyHostToDevice), "H2D mel lifter");
     if (!ok) { if (sp->d_tables) (void)hipFree(sp->d_tables); delete sp; return CLX_API_ERROR; }
     sp->dev = clx_mel_args(sp->t, (const float*)d, (const float*)(d + nb), (const uint32_t*)(d + nb + nf));
+    sp->qdev = clx_mel_qargs(sp->t, (const float*)(d + nb + nf + ne), (const float*)(d + nb + nf + ne + nd));
     std::vector<float>().swap(sp->t.basis);                    // (the device has it; the host copy is not needed again)
     ctx->mel_specs.push_back(sp);
     *spec = sp;
@@ -1609,6 +1615,12 @@ extern "C" int clx_mel_create_framed(clx_ctx* ctx, uint32_t n_fft, uint32_t win_
                                      uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_frame_opts* opts,
                                      clx_mel_spec** spec) {
     return clx_mel_create_any(ctx, n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, nullptr, opts, spec);
+}
+
+extern "C" int clx_mel_create_cepstral(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank,
+                                       uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_frame_opts* opts,
+                                       const clx_mel_cep_opts* cep, clx_mel_spec** spec) {
+    return clx_mel_create_any(ctx, n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, nullptr, opts, spec, true, cep);
 }
 
 extern "C" void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec) {
@@ -1652,7 +1664,11 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_up, stream));
     ctx->mel_used = true;                                      // (from here on the staging and the table are in use)
-    if (clx_mel_is_f(spec->t)) {
+    if (clx_mel_is_q(spec->t)) {
+        hipLaunchKernelGGL(clx_k_mel_q, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                           (const uint32_t*)ctx->d_mel, spec->dev, clx_mel_fargs(spec->t), spec->qdev, n_groups, window_len, n_frames, layout,
+                           (float*)d_out);
+    } else if (clx_mel_is_f(spec->t)) {
         hipLaunchKernelGGL(clx_k_mel_f, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
                            (const uint32_t*)ctx->d_mel, spec->dev, clx_mel_fargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
     } else if (!is_c) {

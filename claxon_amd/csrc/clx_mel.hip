@@ -51,7 +51,18 @@
 // a bank that stops below the Nyquist bin and the whole-frame rule need no kernel of their own: the table has rows (slices) for
 // win_length taps and passes for n_bins bins only, and clx_k_mel runs a framed spec that does not condition.
 //
-// clx_mel_build / clx_mel_build_framed / clx_mel_check / clx_mel_fill / clx_mel_fill_c are the host side (plain C++, shared with the
+// clx_k_mel_q is the fourth: a cepstral spec (claxon_hip.h, clx_mel_create_cepstral), which is Kaldi's MFCC.  It frames
+// and conditions as clx_k_mel_f does and differs in two places.  The prologue: with `energy` the 8 lanes of a frame make a second pass
+// over it once the means have crossed the block, lane i adding the squares of d[i], d[i + 8], ... with one fmaf each; three shuffles
+// fold them, and the frame's log energy waits in a register of the frame's first lane.  The last step: a lane keeps its finished
+// log-mel cells -- at most 16, which is where the limit of 128 bands comes from -- in the registers the GEMM's accumulators have
+// left; behind one barrier (P has been read) they go to Y[f][m] in the staging area, rows kYRow = 129 floats apart (1 mod 32: the 32
+// frames a half-wave reads at one m lie in 32 banks), and the 32 log energies go behind them; behind a second barrier cell (i, f)
+// of the n_ceps x 32 output cells, dealt to the lanes along the output row as the band cells are, runs dct[i][.] . Y[f][.] as one
+// fmaf chain, m ascending, the dct row from global memory (it is a few KiB and stays in the caches), and applies the lifter or
+// takes the energy.  One pass only: a cepstral spec has n_bins <= 256, for a cepstral output has no rows to park partial band sums in.
+//
+// clx_mel_build / clx_mel_build_framed / clx_mel_build_cepstral / clx_mel_check / clx_mel_fill / clx_mel_fill_c are the host side (plain C++, shared with the
 // wave simulator).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -79,6 +90,15 @@ struct clx_mel_fdev {
     float preemph;
 };
 
+// what clx_k_mel_q needs on top of both (passed by value, uniform): the DCT [n_ceps][n_mels], the lifter [n_ceps] (null: none), whether
+// row 0 is the frame's log energy, the factor of the energy and the floor of it (0: none)
+struct clx_mel_qdev {
+    const float* dct;
+    const float* lifter;
+    uint32_t n_ceps, energy;
+    float energy_scale, energy_floor;
+};
+
 // what clx_k_mel_c needs on top of it (passed by value): P = n_fft / 2 of a centred spec (else 0), zero = 1 for CLX_MEL_PAD_ZERO
 // of a centred spec, range = 1 for a range-scaled one
 struct clx_mel_cdev {
@@ -93,6 +113,9 @@ struct clx_mel_tables {
     float range_width = 0.f, shift = 0.f, scale = 0.f;
     uint32_t win = 0, remove_dc = 0, whole = 0;              // clx_mel_create_framed: win_length (else n_fft) and clx_mel_frame_opts
     float preemph = 0.f;
+    uint32_t n_ceps = 0, has_lifter = 0, energy = 0;         // clx_mel_create_cepstral: clx_mel_cep_opts (n_ceps == 0: not cepstral)
+    float energy_scale = 1.f, energy_floor = 0.f;
+    std::vector<float> dct, lifter;
     std::vector<float> basis, fbank;
     std::vector<uint32_t> ends;
 };
@@ -100,10 +123,12 @@ struct clx_mel_tables {
 namespace clx_mel {
 
 constexpr uint32_t kThreads = 256u, kF = 32u, kBins = 256u, kKS = 16u, kRow = 2u * kBins, kXsRow = 36u, kPRow = 260u, kMaxMels = 256u;
+constexpr uint32_t kMaxCepMels = 128u, kYRow = kMaxCepMels + 1u, kQCells = kMaxCepMels * kF / kThreads;   // clx_k_mel_q: 16 cells a lane
 constexpr uint32_t kStage = kKS * kRow + kKS * kXsRow;          // floats of the staging area (P aliases it)
 constexpr uint32_t kLdsBytes = kStage * 4u;                     // 35 072
 constexpr uint32_t kRangeVecs = 1024u;                          // 16-byte vectors of a clx_k_mel_range block: 4 per lane
 static_assert(kF * kPRow <= kStage, "P fits in the staging area");
+static_assert(kF * kYRow + kF <= kStage, "Y and the 32 log energies fit in the staging area");
 static_assert(kThreads == 8u * kF, "the prologue of clx_k_mel_f sums a frame with 8 lanes");
 static_assert(2u * kLdsBytes <= 160u * 1024u, "two workgroups share a CU's LDS");
 
@@ -172,25 +197,27 @@ __device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mel
 // Block b: frame group b % n_groups of window b / n_groups (clx_mel_check gives n_groups).  `audio` is [B, L], vframes[k] =
 // valid_frames[k] <= n_frames, `out` is [B, n_mels, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_mels] (CLX_WINDOW_TC).  kC: the
 // centred and/or ranged form (X, lim[k] and wmax[k] are used by it alone).  kFr: the conditioning form (F is used by it alone).
+// kQ (with kFr): the cepstral form (Q is used by it alone); `out` has n_ceps in place of n_mels.
 namespace clx_mel {
-template <bool kC, bool kFr>
+template <bool kC, bool kFr, bool kQ>
 __device__ __forceinline__ void body(const float* __restrict__ audio, const uint32_t* __restrict__ vframes,
-                                     const clx_mel_dev S, const clx_mel_cdev X, const clx_mel_fdev F, const uint32_t* __restrict__ lim,
+                                     const clx_mel_dev S, const clx_mel_cdev X, const clx_mel_fdev F, const clx_mel_qdev Q, const uint32_t* __restrict__ lim,
                                      uint32_t* wmax, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout, float* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float s_stage[kStage];
     const uint32_t tid = threadIdx.x, k = blockIdx.x / n_groups, f0 = (blockIdx.x - k * n_groups) * kF;
     const uint32_t vf = vframes[k];
     const uint32_t nf_out = n_frames - f0 < kF ? n_frames - f0 : kF;                 // the group's frames that exist
     const uint32_t nf_live = vf > f0 ? (vf - f0 < kF ? vf - f0 : kF) : 0u;           // ... and those that are computed (<= nf_out)
+    const uint32_t n_out = kQ ? Q.n_ceps : S.n_mels;           // the rows of the output
     const uint32_t cells = S.n_mels * kF;
-    float* const o = out + (uint64_t)k * S.n_mels * n_frames;
+    float* const o = out + (uint64_t)k * n_out * n_frames;
     float y0 = 0.f;                                            // a dead cell: +0.0, or the silence value of a ranged spec
     if constexpr (kC) if (X.range) y0 = finish(S.mode, S.floor, 0.f);
     if (nf_live == 0u) {
-        for (uint32_t c = tid; c < cells; c += kThreads) {
+        for (uint32_t c = tid; c < n_out * kF; c += kThreads) {
             uint32_t m, f;
-            cell(c, layout, S.n_mels, &m, &f);
-            if (f < nf_out) o[layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * S.n_mels + m] = kC ? y0 : 0.f;
+            cell(c, layout, n_out, &m, &f);
+            if (f < nf_out) o[layout == CLX_WINDOW_CT ? (uint64_t)m * n_frames + f0 + f : (uint64_t)(f0 + f) * n_out + m] = kC ? y0 : 0.f;
         }
         if constexpr (kC) if (X.range && tid == 0u) atomicMax(wmax + k, enc(y0));      // (every cell of the block is y0)
         return;
@@ -233,6 +260,27 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
             __syncthreads();
             mu0 = s_stage[x_f];
             mu1 = s_stage[x_f + 16u];                          // (read before the first round's barrier, behind which the staging begins)
+        }
+    }
+    // kQ: the log energy of frame tid >> 3 (every one of the frame's 8 lanes has it; lane 0 of them hands it on in the last step)
+    float le = 0.f;
+    if constexpr (kQ) {
+        if (Q.energy) {                                        // (uniform over the block)
+            const uint32_t sf = tid >> 3;
+            float e = 0.f;
+            if (sf < nf_live) {
+                const float* const fr = a + (uint64_t)(f0 + sf) * S.hop;
+                const float mu = F.remove_dc ? s_stage[sf] : 0.f;   // (as mu0 and mu1: read before the first round's barrier)
+                for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) {
+                    const float d = F.remove_dc ? sub_rn(fr[n], mu) : fr[n];
+                    e = fmaf(d, d, e);
+                }
+            }
+            e = add_rn(e, __shfl_xor(e, 4));
+            e = add_rn(e, __shfl_xor(e, 2));
+            e = add_rn(e, __shfl_xor(e, 1));
+            le = logf(fmaxf(mul_rn(e, Q.energy_scale), 1.1920928955078125e-07f));   // (FLT_EPSILON)
+            if (Q.energy_floor > 0.f) { const float lf = logf(Q.energy_floor); if (le < lf) le = lf; }
         }
     }
 
@@ -331,6 +379,49 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
             }
         }
         __syncthreads();
+        if constexpr (kQ) {                                    // (one pass: n_bins <= 256)
+            float y[kQCells];
+#pragma unroll
+            for (uint32_t r = 0; r < kQCells; ++r) {
+                y[r] = 0.f;
+                const uint32_t c = tid + r * kThreads;
+                uint32_t m, f;
+                cell(c, layout, S.n_mels, &m, &f);
+                if (c < cells && f < nf_live) {
+                    float acc = 0.f;
+                    const uint32_t e0 = S.ends[2u * m], e1 = S.ends[2u * m + 1u];
+                    const float* const fb = S.fbank + (uint64_t)m * S.n_bins;
+                    const float* const pr = P + f * kPRow;
+                    for (uint32_t j = e0; j < e1; ++j) acc = fmaf(fb[j], pr[j], acc);
+                    y[r] = finish(S.mode, S.floor, acc);
+                }
+            }
+            __syncthreads();                                   // (P has been read)
+            float* const Y = s_stage;
+#pragma unroll
+            for (uint32_t r = 0; r < kQCells; ++r) {
+                const uint32_t c = tid + r * kThreads;
+                uint32_t m, f;
+                cell(c, layout, S.n_mels, &m, &f);
+                if (c < cells) Y[f * kYRow + m] = y[r];
+            }
+            if (Q.energy && (tid & 7u) == 0u) Y[kF * kYRow + (tid >> 3)] = le;
+            __syncthreads();
+            for (uint32_t c = tid; c < Q.n_ceps * kF; c += kThreads) {
+                uint32_t i, f;
+                cell(c, layout, Q.n_ceps, &i, &f);
+                if (f >= nf_out) continue;
+                float* const at = o + (layout == CLX_WINDOW_CT ? (uint64_t)i * n_frames + f0 + f : (uint64_t)(f0 + f) * Q.n_ceps + i);
+                if (f >= nf_live) { *at = 0.f; continue; }
+                if (Q.energy && i == 0u) { *at = Y[kF * kYRow + f]; continue; }
+                const float* const dr = Q.dct + (uint64_t)i * S.n_mels;
+                const float* const yr = Y + f * kYRow;
+                float acc = 0.f;
+                for (uint32_t m = 0; m < S.n_mels; ++m) acc = fmaf(dr[m], yr[m], acc);
+                *at = Q.lifter ? mul_rn(acc, Q.lifter[i]) : acc;
+            }
+            break;
+        }
         const uint32_t j0 = p * kBins, j1 = j0 + kBins;
         const bool last = p + 1u == S.n_pass;
         for (uint32_t c = tid; c < cells; c += kThreads) {
@@ -380,14 +471,22 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
 extern "C" __global__ __launch_bounds__(256) void clx_k_mel(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
                                                             uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
                                                             float* __restrict__ out) {
-    clx_mel::body<false, false>(audio, vframes, S, clx_mel_cdev(), clx_mel_fdev(), nullptr, nullptr, n_groups, L, n_frames, layout, out);
+    clx_mel::body<false, false, false>(audio, vframes, S, clx_mel_cdev(), clx_mel_fdev(), clx_mel_qdev(), nullptr, nullptr, n_groups, L, n_frames, layout, out);
 }
 
 // The conditioning form of a framed spec (remove_dc and / or preemph > 0); otherwise clx_k_mel's arguments.
 extern "C" __global__ __launch_bounds__(256) void clx_k_mel_f(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
                                                               clx_mel_fdev F, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
                                                               float* __restrict__ out) {
-    clx_mel::body<false, true>(audio, vframes, S, clx_mel_cdev(), F, nullptr, nullptr, n_groups, L, n_frames, layout, out);
+    clx_mel::body<false, true, false>(audio, vframes, S, clx_mel_cdev(), F, clx_mel_qdev(), nullptr, nullptr, n_groups, L, n_frames, layout, out);
+}
+
+// The cepstral form (every cepstral spec, whether it conditions or not): clx_k_mel_f's arguments and Q; `out` is [B, n_ceps, n_frames]
+// or [B, n_frames, n_ceps].
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel_q(const float* __restrict__ audio, const uint32_t* __restrict__ vframes, clx_mel_dev S,
+                                                              clx_mel_fdev F, clx_mel_qdev Q, uint32_t n_groups, uint32_t L, uint32_t n_frames,
+                                                              uint32_t layout, float* __restrict__ out) {
+    clx_mel::body<false, true, true>(audio, vframes, S, clx_mel_cdev(), F, Q, nullptr, nullptr, n_groups, L, n_frames, layout, out);
 }
 
 // The centred and/or ranged form.  `table` is the call's device table: vframes[B], then lim[B] (the end of what a tap may load of
@@ -396,7 +495,7 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel_f(const float* __res
 extern "C" __global__ __launch_bounds__(256) void clx_k_mel_c(const float* __restrict__ audio, uint32_t* table, uint32_t n_windows, clx_mel_dev S,
                                                               clx_mel_cdev X, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout,
                                                               float* __restrict__ out) {
-    clx_mel::body<true, false>(audio, table, S, X, clx_mel_fdev(), table + n_windows, table + 2u * (uint64_t)n_windows, n_groups, L, n_frames, layout, out);
+    clx_mel::body<true, false, false>(audio, table, S, X, clx_mel_fdev(), clx_mel_qdev(), table + n_windows, table + 2u * (uint64_t)n_windows, n_groups, L, n_frames, layout, out);
 }
 
 // The range step, in place: out[k][c] = fl32(fl32(max(out[k][c], fl32(max_k - D)) + shift) * scale) for the `cells` cells of window
@@ -493,6 +592,28 @@ inline std::string clx_mel_build_framed(uint32_t n_fft, uint32_t win_length, uin
     return std::string();
 }
 
+// The host side of clx_mel_create_cepstral: the framed spec's checks and tables, then the cepstral options' checks and copies of the
+// DCT and the lifter.
+inline std::string clx_mel_build_cepstral(uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank, uint32_t n_bins,
+                                          uint32_t n_mels, uint32_t mode, float floor, clx_mel_tables* t, const clx_mel_frame_opts* fopts,
+                                          const clx_mel_cep_opts* q) {
+    if (!q) return "clx_mel_create_cepstral: null cepstral options";
+    const std::string why = clx_mel_build_framed(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, t, nullptr, fopts);
+    if (!why.empty()) return why;
+    if (n_mels > clx_mel::kMaxCepMels) return "clx_mel_create_cepstral: a cepstral spec has at most 128 bands";
+    if (n_bins > clx_mel::kBins) return "clx_mel_create_cepstral: a cepstral spec has at most 256 bins";
+    if (q->n_ceps < 1u || q->n_ceps > n_mels) return "clx_mel_create_cepstral: n_ceps must be 1..n_mels";
+    if (!q->dct) return "clx_mel_create_cepstral: null dct";
+    if (q->energy > 1u) return "clx_mel_create_cepstral: energy must be 0 or 1";
+    if (!std::isfinite(q->energy_scale) || !(q->energy_scale > 0.f)) return "clx_mel_create_cepstral: energy_scale must be finite and greater than 0";
+    if (!std::isfinite(q->energy_floor) || !(q->energy_floor >= 0.f)) return "clx_mel_create_cepstral: energy_floor must be finite and not negative";
+    t->n_ceps = q->n_ceps; t->energy = q->energy; t->energy_scale = q->energy_scale; t->energy_floor = q->energy_floor > 0.f ? q->energy_floor : 0.f;
+    t->dct.assign(q->dct, q->dct + (size_t)q->n_ceps * n_mels);
+    t->has_lifter = q->lifter ? 1u : 0u;
+    if (q->lifter) t->lifter.assign(q->lifter, q->lifter + q->n_ceps);
+    return std::string();
+}
+
 inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* window, const float* fbank, uint32_t n_mels, uint32_t mode,
                                  float floor, clx_mel_tables* t, const clx_mel_opts* opts = nullptr) {
     return clx_mel_build_framed(n_fft, n_fft, hop, window, fbank, n_fft / 2u + 1u, n_mels, mode, floor, t, opts, nullptr);
@@ -555,6 +676,20 @@ inline clx_mel_fdev clx_mel_fargs(const clx_mel_tables& t) {
     f.remove_dc = t.remove_dc; f.preemph = t.preemph;
     return f;
 }
+
+// clx_k_mel_q runs a cepstral spec
+inline bool clx_mel_is_q(const clx_mel_tables& t) { return t.n_ceps != 0u; }
+
+// (dct and lifter: where the spec's copies are, for the kernel; lifter is ignored for a spec without one)
+inline clx_mel_qdev clx_mel_qargs(const clx_mel_tables& t, const float* dct, const float* lifter) {
+    clx_mel_qdev q;
+    q.dct = dct; q.lifter = t.has_lifter ? lifter : nullptr;
+    q.n_ceps = t.n_ceps; q.energy = t.energy; q.energy_scale = t.energy_scale; q.energy_floor = t.energy_floor;
+    return q;
+}
+
+// the rows of a spec's output: n_ceps of a cepstral spec, else n_mels
+inline uint32_t clx_mel_rows(const clx_mel_tables& t) { return t.n_ceps ? t.n_ceps : t.n_mels; }
 
 inline bool clx_mel_is_c(const clx_mel_tables& t) { return t.center != 0u || t.range != 0u; }
 

@@ -549,6 +549,41 @@ typedef struct { uint32_t remove_dc, whole_frames; float preemph; } clx_mel_fram
 int  clx_mel_create_framed(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window /*[win_length]*/,
                            const float* fbank /*[n_mels][n_bins]*/, uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor,
                            const clx_mel_frame_opts* opts, clx_mel_spec** spec);
+/* Cepstral specs: a framed spec whose log-mel cells go through a DCT and a lifter inside the feature kernel, with the frame's log
+ * energy in row 0 if asked for (clx_k_mel_q).  This is Kaldi's MFCC (compute-mfcc-feats,
+ * torchaudio.compliance.kaldi.mfcc): 23 bands, 13 coefficients, the orthonormal DCT-II, the lifter 1 + 11 sin(pi i / 22), and
+ * use_energy with raw_energy.  The spec is clx_mel_create_framed's (opts == NULL meaning all zero, as there) and cep, which is
+ * required: n_ceps in 1..n_mels, a float32 dct[n_ceps][n_mels], a float32 lifter[n_ceps] or NULL for none, energy 0 or 1,
+ * energy_scale finite and > 0, energy_floor finite and >= 0 (0: none).  The handle is an ordinary clx_mel_spec for clx_mel_windows
+ * and clx_mel_destroy; the output has n_ceps rows in place of n_mels: [B, n_ceps, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_ceps]
+ * (CLX_WINDOW_TC).
+ *
+ *   log-mel    Y[f][m] = finish(M_m) of frame f is clx_mel_create_framed's, word for word: the same frames, conditioning, basis,
+ *              sums in the same order and the same last step (mode and floor; CLX_MEL_POWER gives the DCT of the band sums).
+ *   cepstrum   C[f][i] = sum_m dct[i][m] Y[f][m] as one fmaf chain in float32, m ascending, from +0.0.  With a lifter
+ *              C[f][i] = fl32(C[f][i] * lifter[i]), rounded once and not contracted (Kaldi's MulElements behind its GEMV).
+ *   energy     (energy == 1; Kaldi's use_energy with raw_energy=true.)  d[n] is the frame after the mean's removal (if remove_dc:
+ *              d[n] = fl32(x[n] - mu), mu as above) and before pre-emphasis and the window.  e_i = fmaf(d[n], d[n], e_i) over
+ *              n = i, i+8, .. ascending for i = 0..7, from +0.0; e = ((e_0 + e_4) + (e_2 + e_6)) + ((e_1 + e_5) + (e_3 + e_7)), each sum
+ *              rounded once; E = fl32(e * energy_scale) (a window in the int16 range carries 32768, the energy needs its
+ *              square, a power of two); le = logf(max(E, FLT_EPSILON)); if energy_floor > 0 and le < logf(energy_floor),
+ *              le = logf(energy_floor).  Row 0 of the output is le in place of C[f][0]; it is not liftered.
+ *   bound      With dY_m the bound of Y_m (dM through the logarithm), for ANY order of the sum:
+ *              dC_i = sum_m |dct[i][m]| dY_m + g(n_mels+1) sum_m |dct[i][m] Y_m|, and one more rounding for the lifter.
+ *   validity   clx_mel_create_framed's rules.  A dead frame is +0.0 in all n_ceps rows and is not computed; no float outside a
+ *              live frame is read; the call writes all of d_out.
+ *
+ * Every cepstral spec runs clx_k_mel_q, whether it conditions its frames or not.  A lane of that kernel keeps its share of a frame
+ * group's log-mel cells in 16 registers until the group's power spectrum has been read, hence n_mels <= 128; and a spec of more
+ * than one pass of 256 bins parks its partial band sums in the output's rows, which a cepstral output does not have, hence
+ * n_bins <= 256.  CLX_API_ERROR, each by a text of its own, for clx_mel_create_framed's refusals and for cep == NULL, n_mels > 128,
+ * n_bins > 256, n_ceps outside 1..n_mels, dct == NULL, energy other than 0 or 1, an energy_scale that is not finite or not > 0 and
+ * an energy_floor that is not finite or negative.  The definition restates Kaldi's; it has not been compared with a Kaldi binary. */
+typedef struct { uint32_t n_ceps; const float* dct /*[n_ceps][n_mels]*/; const float* lifter /*[n_ceps] or NULL*/; uint32_t energy;
+                 float energy_scale, energy_floor; } clx_mel_cep_opts;
+int  clx_mel_create_cepstral(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window /*[win_length]*/,
+                             const float* fbank /*[n_mels][n_bins]*/, uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor,
+                             const clx_mel_frame_opts* opts, const clx_mel_cep_opts* cep, clx_mel_spec** spec);
 void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
 /* The features of d_audio [n_windows][window_len] (device, float32) into d_out (device, float32), asynchronously on `stream`
  * (NULL: the context's).  valid is a host array; it is staged like the window table of clx_gather_windows: pinned staging, a
@@ -558,7 +593,8 @@ void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
  * n_frames == 0 succeeds and launches nothing.  The spec decides the kernel, the length condition and the valid_frames rule: a
  * centred or ranged spec runs clx_k_mel_c (its table also carries, per window, the end of what may be loaded and the encoded
  * maximum, initialised by the upload), a ranged one clx_k_mel_range behind it; a framed spec is held to win_length in place of
- * n_fft and to its own valid_frames rule, and runs clx_k_mel_f if it conditions its frames. */
+ * n_fft and to its own valid_frames rule, and runs clx_k_mel_f if it conditions its frames; a cepstral spec is a framed spec that
+ * runs clx_k_mel_q and writes n_ceps rows in place of n_mels. */
 int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
                      const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
