@@ -241,3 +241,21 @@ def reference(audio, window, fbank, N, H, n_frames, remove_dc, c, floor, dct, li
         C64, dC = C64 * l[None, None, :], dC * np.abs(l)[None, None, :]
         dC = dC + _ulp(np.abs(C64) + dC)
     return C64, dC
+
+
+def reference_power(audio, window, fbank, N, H, n_frames, remove_dc, c, dct, lifter=None):
+    """(C64, dC), each [B, n_frames, n_ceps] in float64, for a cepstral spec in power mode, where the cells that enter the DCT are
+    the band sums themselves: with (M64, dM) from simlib_melk.reference and D the float32 DCT, C64 = M64 @ D.T.  The kernel's cell
+    Y_m is a float32 with |Y_m - M64_m| <= dM_m, and its chain of n_mels fmaf from +0.0 adds at most g(n_mels) sum_m |D[i][m]| |Y_m|
+    in any order, so dC = dM @ |D|.T + g(n_mels + 1) ((M64 + dM) @ |D|.T) (M64 >= 0).  With a lifter both times |lifter[i]|, and one
+    float32 ulp of the larger end for the product's one rounding."""
+    M64, dM = sk.reference(audio, window, fbank, N, H, n_frames, remove_dc, c)
+    D = np.asarray(np.asarray(dct, dtype=np.float32), dtype=np.float64)
+    n_mels = D.shape[1]
+    C64 = M64 @ D.T
+    dC = dM @ np.abs(D).T + g(n_mels + 1) * ((M64 + dM) @ np.abs(D).T)
+    if lifter is not None:
+        l = np.asarray(np.asarray(lifter, dtype=np.float32), dtype=np.float64)
+        C64, dC = C64 * l[None, None, :], dC * np.abs(l)[None, None, :]
+        dC = dC + _ulp(np.abs(C64) + dC)
+    return C64, dC

@@ -4,7 +4,8 @@ these kernels is a chain of explicit fmaf in a fixed order over tables built on 
 differ in; a difference is a miscompile, a race the simulator's fixed schedule hides, a table that differs between the two host
 compilers, or a contraction.  The float64 definition under its derived bound stays beside the equality as the check that what the
 two share is right (simlib_mel.reference, simlib_resample.assert_close), and the log modes, whose last step is the device's logf /
-log10f, are held to LOG_ULPS of float64 log(max(float64(M), floor)) with M the power output of the same call shape.
+log10f, are held to LOG_ULPS of float64 log(max(float64(M), floor)) with M the power output of the same call shape.  The other four
+mel kernels -- clx_k_mel_c, clx_k_mel_range, clx_k_mel_f and clx_k_mel_q -- are held in the same way in test_gpu_mel_forms.py.
 
 The shapes are those where a device build can go its own way: mel with more than one pass of 256 bins (J = 301; J = 257, a second
 pass of one bin; n_fft 2048, five passes of 128 K-slices), one pass exactly full (J = 256) and hop > n_fft; the resampler going up

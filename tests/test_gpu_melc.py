@@ -9,6 +9,7 @@ import torch
 
 import claxon_amd as cx
 import simlib_mel as sm
+from gpu_guarded import device_out, written
 from test_gpu_mel import NAMES, SHAPES, _native_batch
 from test_gpu_mix import _stream
 
@@ -42,12 +43,14 @@ def _btm(out, layout):
 
 
 def _mel(ctx, spec, a, valid, layout):
-    B = int(a.shape[0])
-    out = torch.full((B, spec.n_mels, T) if layout == "ct" else (B, T, spec.n_mels), float("nan"), dtype=torch.float32, device=a.device)
+    """mel_windows into a guarded slice: [B, T, n_mels] on the host, after the guards' and the fill's checks."""
+    B, n = int(a.shape[0]), int(a.shape[0]) * spec.n_mels * T
+    flat, out = device_out(n, offset_words=1)
     torch.cuda.synchronize()                                 # (the fill first: on torch's default stream the launch goes to the context's own)
-    ctx.mel_windows(spec, a, valid, T, cx._LAYOUTS[layout], out)
+    ctx.mel_windows(spec, a, valid, T, cx._LAYOUTS[layout], out.view((B, spec.n_mels, T) if layout == "ct" else (B, T, spec.n_mels)))
     torch.cuda.synchronize()
-    return _btm(out, layout)
+    o = written(flat, n, (spec.n_fft, spec.hop, spec.n_mels, layout), offset_words=1).view(np.float32)
+    return o.reshape(B, spec.n_mels, T).transpose(0, 2, 1) if layout == "ct" else o.reshape(B, T, spec.n_mels)
 
 
 @pytest.mark.parametrize("pad_mode", ("reflect", "zeros"))

@@ -10,6 +10,7 @@ import torch
 import claxon_amd as cx
 import simlib_mel as sm
 import simlib_melk as sk
+from gpu_guarded import device_out, written
 from test_gpu_mel import NAMES, SHAPES, _native_batch
 from test_gpu_melc import _calls
 from test_gpu_mix import _stream
@@ -46,12 +47,14 @@ def _btm(out, layout):
 
 
 def _mel(ctx, spec, a, valid, layout, n_frames=T):
-    B = int(a.shape[0])
-    out = torch.full((B, spec.n_mels, n_frames) if layout == "ct" else (B, n_frames, spec.n_mels), float("nan"), dtype=torch.float32, device=a.device)
+    """mel_windows into a guarded slice: [B, n_frames, n_mels] on the host, after the guards' and the fill's checks."""
+    B, n = int(a.shape[0]), int(a.shape[0]) * spec.n_mels * n_frames
+    flat, out = device_out(n, offset_words=1)
     torch.cuda.synchronize()                                 # (the fill first: on torch's default stream the launch goes to the context's own)
-    ctx.mel_windows(spec, a, valid, n_frames, cx._LAYOUTS[layout], out)
+    ctx.mel_windows(spec, a, valid, n_frames, cx._LAYOUTS[layout], out.view((B, spec.n_mels, n_frames) if layout == "ct" else (B, n_frames, spec.n_mels)))
     torch.cuda.synchronize()
-    return _btm(out, layout)
+    o = written(flat, n, (spec.win_length, spec.n_fft, spec.hop, spec.n_mels, layout), offset_words=1).view(np.float32)
+    return o.reshape(B, spec.n_mels, n_frames).transpose(0, 2, 1) if layout == "ct" else o.reshape(B, n_frames, spec.n_mels)
 
 
 def _tables(Nw, N, n_mels, n_bins):
