@@ -1465,8 +1465,10 @@ class MelSpec:
         """The spec of Whisper's log_mel_spectrogram: 16 kHz, n_fft 400, hop 160, Slaney mel scale with Slaney normalisation up to
         8 kHz, log10 with floor 1e-10, frames centred with reflection, every cell clamped to the window's maximum - 8.0, then
         (y + 4) / 4.  read_mel(ids, starts, 3000, MelSpec.whisper(ctx)) is the encoder's [B, 80, 3000] input for 30 s crops.  The
-        filterbank is librosa's by formula (mel_fbank); Whisper's own table file is not available to this project and has not been
-        compared with it.  Whisper also drops the last of its 3001 frames; ask for the frames you want."""
+        filterbank is librosa's by formula (mel_fbank): within half a float32 ulp of WhisperFeatureExtractor's mel_filters for 80
+        and 128 bands, cell by cell, and the features are held to that extractor's output (tests/golden/features, DESIGN.md 4.14);
+        Whisper's own table file (mel_filters.npz) is not available to this project.  Whisper also drops the last of its 3001
+        frames; ask for the frames you want."""
         return cls(ctx, 16000, n_fft=400, hop=160, n_mels=n_mels, f_min=0.0, f_max=8000.0, mel_scale="slaney", norm="slaney", mode="log10",
                    floor=1e-10, center=True, pad_mode="reflect", top=8.0, shift=4.0, scale=0.25)
 
@@ -1561,8 +1563,11 @@ class MelSpec:
         in double before its one rounding, and as the conditioning is linear a power-of-two scale gives what Kaldi gives on the
         int16-range input bit for bit.  read_mel(ids, starts, n_frames, MelSpec.kaldi(ctx)) is [B, n_mels, n_frames] ("tc":
         Kaldi's own [n_frames, n_mels]).  dither, use_energy, snip_edges=False, vtln_warp and htk_compat are refused by name (the
-        frame's energy is MelSpec.mfcc's use_energy; fbank's energy column is not provided).  The definition restates Kaldi's and
-        has not been compared with a Kaldi binary."""
+        frame's energy is MelSpec.mfcc's use_energy; fbank's energy column is not provided).  The tables, the definition and the
+        kernel's output are held to the float64 port of torchaudio's Kaldi code in transformers.audio_utils (tests/golden/features,
+        DESIGN.md 4.14); two conventions differ from that port and follow Kaldi: preemphasis is rounded to float32, as Kaldi's
+        BaseFloat is (the port keeps the double 0.97), and the transform is not rounded to complex64.  No Kaldi binary itself has
+        been run, and windows read at another rate than the stream's (the resampled path) are not covered."""
         for name, v in refused.items():
             if name not in cls._KALDI_REFUSED:
                 raise TypeError("MelSpec.kaldi: unknown argument %r" % name)
@@ -1596,7 +1601,9 @@ class MelSpec:
         pre-emphasis and the window), not less than ln(energy_floor) if that is greater than 0; the samples' int16-range scale enters
         the energy as scale ** 2.  read_mel(ids, starts, n_frames, MelSpec.mfcc(ctx)) is [B, n_ceps, n_frames] ("tc": Kaldi's own
         [n_frames, n_ceps]).  dither, snip_edges=False, vtln_warp, htk_compat and raw_energy=False are refused by name.  The
-        definition restates Kaldi's and has not been compared with a Kaldi binary."""
+        cepstra are held to scipy.fft.dct (orthonormal DCT-II) of the outside fbank of MelSpec.kaldi's comparison
+        (tests/golden/features); the lifter formula and the energy row are this project's own reading of Kaldi and
+        have not been checked against an outside implementation, and no Kaldi binary itself has been run."""
         for name, v in refused.items():
             if name not in cls._MFCC_REFUSED:
                 raise TypeError("MelSpec.mfcc: unknown argument %r" % name)

@@ -168,15 +168,18 @@ def basis64(window, N):
     return w * np.cos(ang), -w * np.sin(ang)
 
 
-def reference(audio, window, fbank, N, H, n_frames):
+def reference(audio, window, fbank, N, H, n_frames, spectrum=None):
     """(M64, dM), each [B, n_frames, n_mels] in float64, for audio [B, L] (float32, taken as float64): the band sums of the
-    definition and the bound that holds for a float32 evaluation in any order (claxon_hip.h)."""
+    definition and the bound that holds for a float32 evaluation in any order (claxon_hip.h).  spectrum=np.float32 rounds re and im
+    once before they are squared, as an implementation that keeps its transform in complex64 does (outside_cases.py)."""
     a = np.asarray(audio, dtype=np.float64)
     fb = np.asarray(fbank, dtype=np.float64)
     idx = np.arange(n_frames)[:, None] * H + np.arange(N)[None, :]
     X = a[:, idx]                                            # [B, T, N]
     Cb, Sb = basis64(window, N)
     re, im = X @ Cb.T, X @ Sb.T                              # [B, T, J]
+    if spectrum is not None:
+        re, im = re.astype(spectrum).astype(np.float64), im.astype(spectrum).astype(np.float64)
     A, Bm = np.abs(X) @ np.abs(Cb).T, np.abs(X) @ np.abs(Sb).T
     P = re * re + im * im
     dre, dim = g(N + 2) * A, g(N + 2) * Bm

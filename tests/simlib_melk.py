@@ -156,9 +156,11 @@ def basis64(window, N, n_bins):
     return w * np.cos(ang), -w * np.sin(ang)
 
 
-def reference(audio, window, fbank, N, H, n_frames, remove_dc, c):
+def reference(audio, window, fbank, N, H, n_frames, remove_dc, c, spectrum=None):
     """(M64, dM), each [B, n_frames, n_mels] in float64: the band sums of the framed definition with the conditioning in exact
-    arithmetic on the float32 samples, and the bound that holds for a float32 evaluation in any order (claxon_hip.h)."""
+    arithmetic on the float32 samples, and the bound that holds for a float32 evaluation in any order (claxon_hip.h).
+    spectrum=np.float32 rounds re and im once before they are squared, as an implementation that keeps its transform in complex64
+    does (outside_cases.py)."""
     Nw, fb = len(window), np.asarray(fbank, dtype=np.float64)
     X = frames_of(np.asarray(audio, dtype=np.float64), Nw, H, n_frames)              # [B, T, Nw]
     aX = np.abs(X)
@@ -171,6 +173,8 @@ def reference(audio, window, fbank, N, H, n_frames, remove_dc, c):
     dy = (1 + c) * dmu + g(3) * (aX + c * prev(aX) + (1 + c) * (np.abs(mu) + dmu))
     Cb, Sb = basis64(window, N, fb.shape[1])
     re, im = y @ Cb.T, y @ Sb.T
+    if spectrum is not None:
+        re, im = re.astype(spectrum).astype(np.float64), im.astype(spectrum).astype(np.float64)
     dre = g(Nw + 2) * ((np.abs(y) + dy) @ np.abs(Cb).T) + dy @ np.abs(Cb).T
     dim = g(Nw + 2) * ((np.abs(y) + dy) @ np.abs(Sb).T) + dy @ np.abs(Sb).T
     P = re * re + im * im
