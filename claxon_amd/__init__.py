@@ -102,12 +102,13 @@ EXPORTS = [
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_destroy", "clx_mel_windows",
+    "clx_norm_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -192,6 +193,7 @@ def lib():
     L.clx_mel_destroy.argtypes = [vp, vp]
     L.clx_mel_destroy.restype = None
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.clx_norm_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -743,6 +745,41 @@ class Context:
         self._check(lib().clx_mel_windows(self._h, spec._h, a_ptr, B, L, _np_ptr(valid), int(n_frames), int(layout), o_ptr,
                                           C.c_void_p(handle) if handle else None))
         return out
+
+    def norm_windows(self, data, valid, layout, norm, stats=None, stream=None):
+        """clx_norm_windows: the dense float32 batch `data` -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC) -- normalised in
+        place per window and row over the first valid[k] time steps, by `norm` (a Norm; claxon_hip.h has the definition and the order
+        of the sums); every cell from valid[k] on becomes norm.pad.  `stats`, if given, is a [B, rows, 2] float32 tensor that receives
+        (mean, scale) of every row.  `data` and `stats` are CUDA float32 tensors, or `data` is a (pointer, B, rows, T) tuple and
+        `stats` a pointer.  Asynchronous on `stream` as gather_windows is.  Returns `data`."""
+        if not isinstance(norm, Norm):
+            raise ValueError("norm_windows: norm must be a Norm, not %r" % (norm,))
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("norm_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("norm_windows: valid has %d entries for %d windows" % (valid.size, B))
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("norm_windows: %s is out of range" % name)
+        if hasattr(stats, "data_ptr"):
+            if tuple(stats.shape) != (B, rows, 2) or not stats.is_contiguous() or str(stats.dtype) != "torch.float32":
+                raise ValueError("norm_windows: stats must be a contiguous float32 [B, rows, 2] tensor")
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        s_ptr = stats.data_ptr() if hasattr(stats, "data_ptr") else (int(stats) if stats else None)
+        opts = norm._opts()
+        self._check(lib().clx_norm_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), int(layout), C.byref(opts), s_ptr,
+                                           C.c_void_p(handle) if handle else None))
+        return data
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
         a = _u8(arena)
@@ -1654,6 +1691,63 @@ class MelSpec:
             pass
 
 
+# ---- per-window normalisation -----------------------------------------------------------------------------------------------------
+
+class _NormOpts(C.Structure):            # clx_norm_opts
+    _fields_ = [("mean", C.c_uint32), ("var", C.c_uint32), ("ddof", C.c_uint32), ("eps", C.c_float), ("pad", C.c_float)]
+
+
+class Norm:
+    """What Context.norm_windows and read(..., normalize=) / read_mel(..., normalize=) do to every row of every window, over the
+    row's valid cells (clx_norm_windows, claxon_hip.h): subtract the mean (`mean`), divide by sqrt(variance + eps) (`var`; the
+    variance about the mean, over n - ddof), and set the padding to `pad`.  A plain value: it owns nothing on the device.
+    ValueError for a mean, var or ddof that is not 0 / 1 (or a bool), for mean and var both off, for an eps that is negative or not
+    finite and for a pad that is not finite."""
+
+    def __init__(self, mean=True, var=True, ddof=0, eps=0.0, pad=0.0):
+        for name, v in (("mean", mean), ("var", var), ("ddof", ddof)):
+            if not isinstance(v, (bool, int, np.integer, np.bool_)) or int(v) not in (0, 1):
+                raise ValueError("Norm: %s must be 0 or 1, not %r" % (name, v))
+        if not mean and not var:
+            raise ValueError("Norm: mean and var are both off: nothing to do")
+        for name, v in (("eps", eps), ("pad", pad)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) \
+                    or abs(float(v)) > float(np.finfo(np.float32).max):
+                raise ValueError("Norm: %s must be a finite number, not %r" % (name, v))
+        if float(eps) < 0:
+            raise ValueError("Norm: eps must not be negative, not %r" % (eps,))
+        self.mean, self.var, self.ddof = bool(mean), bool(var), int(ddof)
+        self.eps, self.pad = float(np.float32(eps)), float(np.float32(pad))
+
+    @classmethod
+    def wav2vec2(cls):
+        """Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm (wav2vec 2.0, HuBERT, WavLM): (x - mean) / sqrt(var + 1e-7), padding 0."""
+        return cls(eps=1e-7)
+
+    @classmethod
+    def cmvn(cls, means=True, vars=True):
+        """Speech2TextFeatureExtractor.utterance_cmvn: per band over the valid frames, the variance about the mean with ddof 0 and
+        no epsilon, padding 0; normalize_means / normalize_vars as `means` / `vars`."""
+        return cls(mean=means, var=vars)
+
+    @classmethod
+    def seamless(cls):
+        """SeamlessM4TFeatureExtractor's per-band step: (x - mean) / sqrt(var(ddof=1) + 1e-7)."""
+        return cls(ddof=1, eps=1e-7)
+
+    def _opts(self):
+        return _NormOpts(int(self.mean), int(self.var), self.ddof, self.eps, self.pad)
+
+    def __repr__(self):
+        return "Norm(mean=%r, var=%r, ddof=%d, eps=%r, pad=%r)" % (self.mean, self.var, self.ddof, self.eps, self.pad)
+
+    def __eq__(self, other):
+        return isinstance(other, Norm) and (self.mean, self.var, self.ddof, self.eps, self.pad) == (other.mean, other.var, other.ddof, other.eps, other.pad)
+
+    def __hash__(self):
+        return hash((self.mean, self.var, self.ddof, self.eps, self.pad))
+
+
 # ---- sample windows from resident streams -----------------------------------------------------------------------------------------
 
 _LAYOUTS = {"tc": WINDOW_TC, "ct": WINDOW_CT}
@@ -1746,7 +1840,7 @@ class StreamSet:
                 out[s] = (int(self._lengths[s]) * n + o - 1) // o
         return torch.from_numpy(out)
 
-    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None):
+    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None, normalize=None):
         """A batch of windows: window k is samples [starts[k], starts[k] + length) of stream stream_ids[k], positions counted as load()
         counts them (by cumulative block size in frame order; the frame headers' sample numbers are not consulted).  Returns (float32
         tensor on the context's GPU, contiguous: [B, length, C] for layout "tc", [B, C, length] for "ct"; valid): valid[k] =
@@ -1773,7 +1867,13 @@ class StreamSet:
         mono stream is copied to each of the K channels.  valid, the frames decoded, the plan and the run do not change; where some
         window's stream has another count than K, one clx_mix_windows launch takes the place of the gather or the resampler.
         ValueError for a K that is not a whole number in 1..8 and for a window whose stream has neither K channels nor one, with K not
-        1."""
+        1.
+
+        With normalize=Norm(...) every window is then normalised per channel over its valid[k] samples (after resampling and
+        channels=): one clx_norm_windows call on the result, queued behind the launch that cut the windows; the samples from valid[k]
+        on become the Norm's pad.  The return value is the same pair.  ValueError for a normalize that is not a Norm."""
+        if normalize is not None and not isinstance(normalize, Norm):
+            raise ValueError("read: normalize must be a Norm or None, not %r" % (normalize,))
         import torch
         if self._descs is None:
             raise ValueError("read: the stream set is closed")
@@ -1865,10 +1965,12 @@ class StreamSet:
             else:
                 self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
                                           _LAYOUTS[layout], out)
+        if normalize is not None and ch > 0:
+            self.ctx.norm_windows(out, valid, _LAYOUTS[layout], normalize)
         return out, torch.from_numpy(valid)
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -1878,7 +1980,13 @@ class StreamSet:
         must be None or that L.  Returns (float32 tensor on the context's GPU: [B, n_out, n_frames] for layout "ct",
         [B, n_frames, n_out] for "tc", n_out = spec.n_out: n_mels, or n_ceps of a cepstral spec; valid_frames): valid_frames[k] (int64 tensor) = spec.valid_frames(valid[k], n_frames) with
         valid[k] the window's samples inside its stream; a frame from there on is zeros, whatever the mode -- the scaled silence value
-        for a spec with top.  The launches are queued behind read()'s, on the stream read() uses (gather_windows has the rule)."""
+        for a spec with top.  The launches are queued behind read()'s, on the stream read() uses (gather_windows has the rule).
+
+        With normalize=Norm(...) the features are then normalised per output row over the window's valid_frames[k] frames, in either
+        layout (utterance CMVN): one clx_norm_windows call behind the spec's own steps, a ranged spec's range step included; the
+        frames from valid_frames[k] on become the Norm's pad.  ValueError for a normalize that is not a Norm."""
+        if normalize is not None and not isinstance(normalize, Norm):
+            raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
         import torch
         if layout not in _LAYOUTS:
             raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
@@ -1906,7 +2014,10 @@ class StreamSet:
                           device=audio.device)
         valid = valid.numpy()
         self.ctx.mel_windows(spec, audio.view(B, L), valid, n_frames, _LAYOUTS[layout], out)
-        return out, torch.from_numpy(spec.valid_frames(valid, n_frames))
+        vf = spec.valid_frames(valid, n_frames)
+        if normalize is not None:
+            self.ctx.norm_windows(out, vf, _LAYOUTS[layout], normalize)
+        return out, torch.from_numpy(vf)
 
 
 def open_streams(ctx, streams):

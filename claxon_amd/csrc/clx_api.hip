@@ -13,6 +13,7 @@
 #include "clx_window.hip"
 #include "clx_mix.hip"                  // (brings clx_resample.hip with it)
 #include "clx_mel.hip"
+#include "clx_norm.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -272,6 +273,12 @@ struct clx_ctx {
     uint32_t* d_mel = nullptr; uint32_t* h_mel = nullptr; size_t mel_cap = 0;
     std::vector<void*> mel_old_dev, mel_old_host;
     hipEvent_t ev_mel_up = nullptr, ev_mel_done = nullptr; bool mel_used = false;
+    // clx_norm_windows: the call's valid[] on the device with its pinned staging and its two events, by the same rules, and the
+    // table of the call's double partial sums (device only: the kernels write it before they read it)
+    uint32_t* d_norm = nullptr; uint32_t* h_norm = nullptr; size_t norm_cap = 0;
+    double* d_norm_part = nullptr; size_t norm_part_cap = 0;
+    std::vector<void*> norm_old_dev, norm_old_host;
+    hipEvent_t ev_norm_up = nullptr, ev_norm_done = nullptr; bool norm_used = false;
 };
 
 struct clx_mel_spec {
@@ -458,6 +465,12 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     for (void* p : ctx->mel_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->mel_old_host) if (p) (void)hipHostFree(p);
     for (clx_mel_spec* sp : ctx->mel_specs) { if (sp->d_tables) (void)hipFree(sp->d_tables); delete sp; }
+    if (ctx->norm_used) (void)hipEventSynchronize(ctx->ev_norm_done);
+    if (ctx->ev_norm_up) (void)hipEventDestroy(ctx->ev_norm_up);
+    if (ctx->ev_norm_done) (void)hipEventDestroy(ctx->ev_norm_done);
+    ctx->norm_old_dev.push_back(ctx->d_norm); ctx->norm_old_dev.push_back(ctx->d_norm_part); ctx->norm_old_host.push_back(ctx->h_norm);
+    for (void* p : ctx->norm_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->norm_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1686,6 +1699,69 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_done, stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_norm_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid, uint32_t layout,
+                                const clx_norm_opts* opts, void* d_stats, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_norm_plan pl;
+    const char* why = clx_norm_check(d_data, n_windows, rows, T, valid, layout, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_chunks == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_norm_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_norm_up, hipEventDisableTiming));
+    if (!ctx->ev_norm_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_norm_done, hipEventDisableTiming));
+    const bool grow_tab = n_windows > ctx->norm_cap, grow_part = pl.partials > ctx->norm_part_cap;
+    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
+        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
+        double* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc norm partial sums")) return CLX_API_ERROR;
+        if (ctx->d_norm_part) ctx->norm_old_dev.push_back(ctx->d_norm_part);
+        ctx->d_norm_part = d; ctx->norm_part_cap = want;
+    }
+    if (grow_tab) {
+        const size_t want = n_windows + n_windows / 2 + 64;
+        uint32_t* d = nullptr; uint32_t* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc norm table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc norm table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_norm) { ctx->norm_old_dev.push_back(ctx->d_norm); ctx->norm_old_host.push_back(ctx->h_norm); }
+        ctx->d_norm = d; ctx->h_norm = h; ctx->norm_cap = want;
+    }
+    if (ctx->norm_used) {
+        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_norm_up));   // (the upload only: the earlier launch itself is not waited for)
+        if (!grow_tab || !grow_part) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_norm_done, 0));
+    }
+    memcpy(ctx->h_norm, valid, n_windows * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_norm, ctx->h_norm, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_norm_up, stream));
+    ctx->norm_used = true;                                     // (from here on the staging and the tables are in use)
+    const uint64_t units = (uint64_t)n_windows * rows * pl.n_chunks;
+    const float* x = (const float*)d_data;
+    if (pl.tc) {
+        hipLaunchKernelGGL(clx_k_norm_sum_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
+                           ctx->d_norm_part, rows, T, pl.n_chunks, pl.n_groups);
+        if (opts->var) {
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(clx_k_norm_sq_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
+                               ctx->d_norm_part, rows, T, pl.n_chunks, pl.n_groups);
+        }
+    } else {
+        hipLaunchKernelGGL(clx_k_norm_sum, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
+                           ctx->d_norm_part, rows, T, pl.n_chunks, units);
+        if (opts->var) {
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(clx_k_norm_sq, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
+                               ctx->d_norm_part, rows, T, pl.n_chunks, units);
+        }
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_norm_apply, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_norm::kThreads), 0, stream, (float*)d_data,
+                       (const uint32_t*)ctx->d_norm, (const double*)ctx->d_norm_part, (float*)d_stats, *opts, rows, T, pl.n_chunks, pl.tc,
+                       pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_norm_done, stream));
     return CLX_OK;
 }
 

@@ -597,6 +597,46 @@ void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
  * runs clx_k_mel_q and writes n_ceps rows in place of n_mels. */
 int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
                      const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream);
+/* Per-window mean and variance normalisation of a dense float32 batch, in place on the device: what wav2vec 2.0 / HuBERT / WavLM do
+ * to a waveform (zero mean, unit variance over the valid samples) and what utterance CMVN does to a feature matrix (per band over
+ * the valid frames).  d_data is [n_windows][rows][T] (CLX_WINDOW_CT) or [n_windows][T][rows] (CLX_WINDOW_TC); window k has
+ * n = valid[k] <= T live time steps, the rest is padding.  For window k and row r, with x[t] the row's cells, t < n:
+ *
+ *   S          the sum of (double)x[t] in double, each addition rounded once, in the ORDER below.
+ *   m          (float)(S / n): a double division, then one rounding to float32.  m = +0.0 for n == 0.
+ *   d[t]       fl32(x[t] - m): one float32 subtraction, rounded to nearest.
+ *   Q          the sum of (double)d[t] * (double)d[t] in double (the product is exact in double), in the same ORDER.  The
+ *              variance is always taken about the mean, whatever `mean` is (Speech2Text with normalize_means=False does the same).
+ *   v          (float)(Q / (n - ddof)), and +0.0 where n <= ddof.
+ *   s          sqrtf(fl32(v + eps)): the float32 addition and the square root are both correctly rounded.  With var == 0 the
+ *              second pass is skipped and s counts as 1.
+ *   cell       y = mean ? d[t] : x[t]; then var ? fl32(y / s) : y, the division correctly rounded float32.
+ *   padding    every cell at t >= n becomes `pad`, whatever it held (it is not read by the sums); a window with n == 0 is all `pad`.
+ *   zero       a row with v + eps == 0 gives what IEEE gives: 0 / 0 = NaN, or +-Inf where the row is not centred, as numpy does.
+ *   stats      d_stats (may be NULL) is [n_windows][rows][2] float32 and receives (m, s) of every row, so that a caller can undo
+ *              the step: x = y * s + m.  (n == 0: (0, sqrtf(eps)); var == 0: s = 1.)
+ *
+ *   ORDER      a function of (t, n) alone -- never of the layout, the grid, rows or r -- so CT and TC of the same data give the
+ *              same m, s and cells bit for bit.  The time axis is cut into chunks of 4096 steps: chunk c holds t in
+ *              [4096 c, min(4096 (c + 1), n)).  Inside a chunk there are 64 strands: strand i adds the chunk's cells with
+ *              t = i mod 64 in ascending t, from +0.0.  The 64 strand sums are folded by an xor tree in six steps, d = 32, 16,
+ *              8, 4, 2, 1: a[i] = a[i] + a[i ^ d] for every i at once; a[0] is the chunk's partial sum.  The row's sum is the
+ *              partials of the chunks with a live cell added in ascending c, from +0.0.  No floating-point atomics.
+ *   bound      the S and Q computed are within n * 2^-53 (relative to the sum of the magnitudes) of the exact sums of the same
+ *              terms; DESIGN.md 4.15 carries that through to the cells.
+ *
+ * opts: mean, var and ddof are 0 or 1 and not mean == var == 0; eps is finite and >= 0; pad is finite.  rows is 1..256: the 1..8
+ * channels of a window batch and every n_out a mel spec can have (n_mels <= 256).  valid is a host array, staged as
+ * clx_mel_windows stages it (pinned staging, tables that have to grow are replaced before anything is queued, one event behind
+ * the upload and one behind the last launch), so the call is asynchronous on `stream` (NULL: the context's), returns without
+ * waiting for the device and valid may be reused at once.  The sums wait between the launches in a per-call table of
+ * n_windows * rows * 2 * ceil(T / 4096) doubles that the context keeps.  CLX_API_ERROR, each with a clx_last_error text of its
+ * own, for opts == NULL, a mean, var or ddof other than 0 or 1, mean == var == 0, an eps that is negative or not finite, a pad that
+ * is not finite, an unknown layout, rows outside 1..256, a null d_data or valid, a valid[k] > T and a call with more than 2^31 - 1
+ * chunks.  n_windows == 0 or T == 0 succeeds and launches nothing. */
+typedef struct { uint32_t mean, var, ddof; float eps, pad; } clx_norm_opts;
+int  clx_norm_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid, uint32_t layout,
+                      const clx_norm_opts* opts, void* d_stats, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
