@@ -101,7 +101,7 @@ EXPORTS = [
     "clx_tags_vendor", "clx_tags_count", "clx_tags_get", "clx_tags_lookup", "clx_tags_free", "clx_reader_tags", "clx_reader_open", "clx_reader_new",
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
-    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_destroy", "clx_mel_windows",
+    "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
     "clx_norm_windows",
 ]
 
@@ -190,6 +190,8 @@ def lib():
                                         C.POINTER(vp)]
     L.clx_mel_create_cepstral.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
                                           vp, C.POINTER(vp)]
+    L.clx_mel_create_reflected.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
+                                           vp, C.POINTER(vp)]
     L.clx_mel_destroy.argtypes = [vp, vp]
     L.clx_mel_destroy.restype = None
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
@@ -1445,8 +1447,14 @@ class MelSpec:
     frame's mean removed and pre-emphasised before the window, a bank over the first bins only and whole frames counted
     (clx_mel_create_framed); MelSpec.kaldi() is Kaldi's fbank that way.  With a DCT, MelSpec.framed() builds a cepstral spec
     (clx_mel_create_cepstral): n_ceps rows of cepstra, liftered, with the frame's log energy in row 0 if asked for; MelSpec.mfcc()
-    is Kaldi's MFCC that way.  n_out is the rows of a spec's output: n_ceps of a cepstral spec, n_mels of any other."""
+    is Kaldi's MFCC that way.  n_out is the rows of a spec's output: n_ceps of a cepstral spec, n_mels of any other.
 
+    MelSpec.framed(..., reflect_edges=True) builds a reflected spec (clx_mel_create_reflected): Kaldi's snip_edges=false, where
+    frame t is centred on sample t * hop + hop // 2 of the window's valid samples, which are continued on both sides by reflection
+    with the edge sample repeated, and a window of V valid samples has (V + hop // 2) // hop frames.  MelSpec.kaldi_reflected() and
+    MelSpec.mfcc_reflected() are Kaldi's fbank and MFCC that way; reflect_edges is an attribute of every spec."""
+
+    reflect_edges = False
     n_ceps, dct, lifter, energy, energy_scale, energy_floor = None, None, None, False, 1.0, 0.0    # (not cepstral unless framed() says so)
 
     @property
@@ -1511,7 +1519,7 @@ class MelSpec:
 
     @classmethod
     def framed(cls, ctx, sample_rate, n_fft, win_length, hop, window, fbank, mode="ln", floor=1e-10, remove_dc=False, preemph=0.0,
-               whole_frames=False, dct=None, lifter=None, energy=False, energy_scale=1.0, energy_floor=0.0):
+               whole_frames=False, dct=None, lifter=None, energy=False, energy_scale=1.0, energy_floor=0.0, reflect_edges=False):
         """The general framed spec (clx_mel_create_framed, claxon_hip.h): frames of win_length <= n_fft samples every `hop`, each
         with its own mean removed (remove_dc) and pre-emphasised by `preemph` (0: none; the first tap refers to the frame's own first
         sample), then `window` [win_length] and an n_fft-point transform of which the first n_bins bins go through `fbank`
@@ -1522,7 +1530,12 @@ class MelSpec:
         n_mels cells), times lifter[i] if `lifter` [n_ceps] is given; with `energy` row 0 is instead the logarithm of
         energy_scale times the frame's energy -- taken after the mean's removal and before pre-emphasis and the window, floored at
         FLT_EPSILON -- and not less than ln(energy_floor) if that is greater than 0.  A cepstral spec has at most 128 bands and
-        256 bins.  Without `dct` the other four must be left alone."""
+        256 bins.  Without `dct` the other four must be left alone.
+
+        reflect_edges=True makes it a reflected spec (clx_mel_create_reflected), fbank or cepstral: frame t's tap n is sample
+        t * hop + hop // 2 - win_length // 2 + n of the window's `valid` samples continued on both sides by reflection with the edge
+        sample repeated (as often as it takes), everything behind the frame as without it, and a window has
+        min(n_frames, (valid + hop // 2) // hop) frames.  It cannot be combined with whole_frames=True."""
         for name, v in (("sample_rate", sample_rate), ("n_fft", n_fft), ("win_length", win_length), ("hop", hop)):
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v:
                 raise ValueError("MelSpec.framed: %s must be a whole number, not %r" % (name, v))
@@ -1543,9 +1556,12 @@ class MelSpec:
         self.mode, self.floor = mode, float(np.float32(floor))
         if mode != "power" and not self.floor > 0:
             raise ValueError("MelSpec.framed: floor must be greater than 0 in mode %r" % mode)
-        for name, v in (("remove_dc", remove_dc), ("whole_frames", whole_frames)):
+        for name, v in (("remove_dc", remove_dc), ("whole_frames", whole_frames), ("reflect_edges", reflect_edges)):
             if not isinstance(v, (bool, np.bool_)):
                 raise ValueError("MelSpec.framed: %s must be True or False, not %r" % (name, v))
+        if reflect_edges and whole_frames:
+            raise ValueError("MelSpec.framed: reflect_edges=True cannot be combined with whole_frames=True (a reflected spec counts (valid + hop // 2) // hop frames)")
+        self.reflect_edges = bool(reflect_edges)
         self.remove_dc, self.whole_frames, self.preemph = bool(remove_dc), bool(whole_frames), float(np.float32(preemph))
         if not (math.isfinite(self.preemph) and 0.0 <= self.preemph <= 1.0):
             raise ValueError("MelSpec.framed: preemph must be finite and in 0..1, not %r" % (preemph,))
@@ -1570,7 +1586,16 @@ class MelSpec:
                 raise ValueError("MelSpec.framed: energy_scale must be finite and greater than 0, not %r" % (energy_scale,))
             if not (math.isfinite(self.energy_floor) and self.energy_floor >= 0):
                 raise ValueError("MelSpec.framed: energy_floor must be finite and not negative, not %r" % (energy_floor,))
-        if ctx is not None and self.n_ceps is not None:
+        if ctx is not None and self.reflect_edges:
+            h = C.c_void_p(None)
+            opts = _MelFrameOpts(int(self.remove_dc), 0, self.preemph)
+            cep = None if self.n_ceps is None else _MelCepOpts(self.n_ceps, _np_ptr(self.dct), None if self.lifter is None else _np_ptr(self.lifter),
+                                                               int(self.energy), self.energy_scale, self.energy_floor)
+            ctx._check(lib().clx_mel_create_reflected(ctx._h, self.n_fft, self.win_length, self.hop, _np_ptr(self.window), _np_ptr(self.fbank),
+                                                      self.n_bins, self.n_mels, _MEL_MODES[mode], self.floor, C.byref(opts),
+                                                      None if cep is None else C.byref(cep), C.byref(h)))
+            self._h = h
+        elif ctx is not None and self.n_ceps is not None:
             h = C.c_void_p(None)
             opts = _MelFrameOpts(int(self.remove_dc), int(self.whole_frames), self.preemph)
             cep = _MelCepOpts(self.n_ceps, _np_ptr(self.dct), None if self.lifter is None else _np_ptr(self.lifter), int(self.energy),
@@ -1591,7 +1616,7 @@ class MelSpec:
 
     @classmethod
     def kaldi(cls, ctx, sample_rate=16000, n_mels=80, frame_length_ms=25.0, frame_shift_ms=10.0, low_freq=20.0, high_freq=0.0,
-              preemphasis=0.97, remove_dc_offset=True, window_type="povey", scale=32768.0, **refused):
+              preemphasis=0.97, remove_dc_offset=True, window_type="povey", scale=32768.0, _reflect=False, **refused):
         """Kaldi's fbank (torchaudio.compliance.kaldi.fbank, kaldi-native-fbank, lhotse's Fbank) with its defaults: frames of
         frame_length_ms every frame_shift_ms (400 and 160 samples at 16 kHz), the frame's mean removed, pre-emphasis 0.97, the povey
         window, a transform of the next power of two (512; at most 2048) of which the Nyquist bin is not used, n_mels triangles that
@@ -1605,11 +1630,12 @@ class MelSpec:
         DESIGN.md 4.14); two conventions differ from that port and follow Kaldi: preemphasis is rounded to float32, as Kaldi's
         BaseFloat is (the port keeps the double 0.97), and the transform is not rounded to complex64.  No Kaldi binary itself has
         been run, and windows read at another rate than the stream's (the resampled path) are not covered."""
+        who, only = ("MelSpec.kaldi_reflected", dict(cls._KALDI_REFUSED, snip_edges=False)) if _reflect else ("MelSpec.kaldi", cls._KALDI_REFUSED)
         for name, v in refused.items():
-            if name not in cls._KALDI_REFUSED:
-                raise TypeError("MelSpec.kaldi: unknown argument %r" % name)
-            if isinstance(v, bool) != isinstance(cls._KALDI_REFUSED[name], bool) or v != cls._KALDI_REFUSED[name]:
-                raise ValueError("MelSpec.kaldi: %s=%r is not supported (only %r)" % (name, v, cls._KALDI_REFUSED[name]))
+            if name not in only:
+                raise TypeError("%s: unknown argument %r" % (who, name))
+            if isinstance(v, bool) != isinstance(only[name], bool) or v != only[name]:
+                raise ValueError("%s: %s=%r is not supported (only %r)" % (who, name, v, only[name]))
         if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float, np.integer, np.floating)) or int(sample_rate) != sample_rate or sample_rate < 1:
             raise ValueError("MelSpec.kaldi: sample_rate must be a whole number from 1 up, not %r" % (sample_rate,))
         win_length, hop = int(sample_rate * 0.001 * float(frame_length_ms)), int(sample_rate * 0.001 * float(frame_shift_ms))
@@ -1623,14 +1649,32 @@ class MelSpec:
         window = mel_window_kaldi(window_type, win_length, scale)
         fbank = mel_fbank_kaldi(sample_rate, n_fft, n_mels, low_freq, high_freq)
         return cls.framed(ctx, sample_rate, n_fft, win_length, hop, window, fbank, mode="ln", floor=FLT_EPSILON, remove_dc=bool(remove_dc_offset),
-                          preemph=preemphasis, whole_frames=True)
+                          preemph=preemphasis, whole_frames=not _reflect, reflect_edges=bool(_reflect))
+
+    @classmethod
+    def kaldi_reflected(cls, ctx, *args, **kw):
+        """Kaldi's fbank with --snip-edges=false (lhotse's and kaldifeat's default): MelSpec.kaldi's arguments, defaults and tables,
+        word for word, on reflected frames.  Frame t is centred on sample t * hop + hop // 2: its tap n is sample
+        t * hop + hop // 2 - win_length // 2 + n, and where that lies outside the window's valid samples [0, valid) it is reflected
+        with the edge sample repeated (-1 is 0, valid is valid - 1), as often as it takes.  A window of `valid` samples has
+        (valid + hop // 2) // hop frames, so the frame count follows the sample count and not the frame length.  The reflection is
+        about the crop read_mel cuts, [start, start + valid), not about the stream: Kaldi's features of a whole utterance of T
+        samples need start = 0, n_frames >= (T + hop // 2) // hop and length >= T -- read_mel's default length n_frames * hop can be
+        shorter than T and would cut the utterance and reflect early.  dither, use_energy, vtln_warp and htk_compat are refused by
+        name as for MelSpec.kaldi (snip_edges, if given, must be False).  The reflection and everything behind it are held to numpy's
+        symmetric padding in front of the outside fbank of MelSpec.kaldi's comparison (tests/golden/features); the
+        frame count and the origin hop // 2 - win_length // 2 are this project's reading of Kaldi's feature-window.cc and have not
+        been checked against an outside implementation, and no Kaldi binary itself has been run."""
+        if "_reflect" in kw:
+            raise TypeError("MelSpec.kaldi_reflected: unknown argument '_reflect'")
+        return cls.kaldi(ctx, *args, _reflect=True, **kw)
 
     _MFCC_REFUSED = dict(dither=0.0, snip_edges=True, vtln_warp=1.0, htk_compat=False, raw_energy=True)
 
     @classmethod
     def mfcc(cls, ctx, sample_rate=16000, n_ceps=13, n_mels=23, cepstral_lifter=22.0, use_energy=False, energy_floor=0.0, frame_length_ms=25.0,
              frame_shift_ms=10.0, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc_offset=True, window_type="povey", scale=32768.0,
-             **refused):
+             _reflect=False, **refused):
         """Kaldi's MFCC (compute-mfcc-feats, torchaudio.compliance.kaldi.mfcc, lhotse's Mfcc) with torchaudio's defaults:
         MelSpec.kaldi's frames, conditioning, window and n_mels = 23 bands by its rules, then the first n_ceps = 13 rows of the
         orthonormal DCT-II of the log-mel cells (mel_dct) and the lifter 1 + 0.5 Q sin(pi i / Q) with Q = cepstral_lifter
@@ -1641,39 +1685,54 @@ class MelSpec:
         cepstra are held to scipy.fft.dct (orthonormal DCT-II) of the outside fbank of MelSpec.kaldi's comparison
         (tests/golden/features); the lifter formula and the energy row are this project's own reading of Kaldi and
         have not been checked against an outside implementation, and no Kaldi binary itself has been run."""
+        who, only = ("MelSpec.mfcc_reflected", dict(cls._MFCC_REFUSED, snip_edges=False)) if _reflect else ("MelSpec.mfcc", cls._MFCC_REFUSED)
         for name, v in refused.items():
-            if name not in cls._MFCC_REFUSED:
-                raise TypeError("MelSpec.mfcc: unknown argument %r" % name)
-            if isinstance(v, bool) != isinstance(cls._MFCC_REFUSED[name], bool) or v != cls._MFCC_REFUSED[name]:
-                raise ValueError("MelSpec.mfcc: %s=%r is not supported (only %r)" % (name, v, cls._MFCC_REFUSED[name]))
+            if name not in only:
+                raise TypeError("%s: unknown argument %r" % (who, name))
+            if isinstance(v, bool) != isinstance(only[name], bool) or v != only[name]:
+                raise ValueError("%s: %s=%r is not supported (only %r)" % (who, name, v, only[name]))
         for name, v in (("n_ceps", n_ceps), ("n_mels", n_mels)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError("MelSpec.mfcc: %s must be a whole number, not %r" % (name, v))
+                raise ValueError("%s: %s must be a whole number, not %r" % (who, name, v))
         if not 1 <= int(n_mels) <= 128 or not 1 <= int(n_ceps) <= int(n_mels):
-            raise ValueError("MelSpec.mfcc: need n_mels in 1..128 and n_ceps in 1..n_mels, not %d and %d" % (n_mels, n_ceps))
+            raise ValueError("%s: need n_mels in 1..128 and n_ceps in 1..n_mels, not %d and %d" % (who, n_mels, n_ceps))
         if not isinstance(use_energy, (bool, np.bool_)):
-            raise ValueError("MelSpec.mfcc: use_energy must be True or False, not %r" % (use_energy,))
+            raise ValueError("%s: use_energy must be True or False, not %r" % (who, use_energy,))
         base = cls.kaldi(None, sample_rate=sample_rate, n_mels=int(n_mels), frame_length_ms=frame_length_ms, frame_shift_ms=frame_shift_ms,
                          low_freq=low_freq, high_freq=high_freq, preemphasis=preemphasis, remove_dc_offset=remove_dc_offset,
                          window_type=window_type, scale=scale)
         return cls.framed(ctx, base.sample_rate, base.n_fft, base.win_length, base.hop, base.window, base.fbank, mode="ln", floor=FLT_EPSILON,
-                          remove_dc=base.remove_dc, preemph=base.preemph, whole_frames=True, dct=mel_dct(n_ceps, n_mels),
+                          remove_dc=base.remove_dc, preemph=base.preemph, whole_frames=not _reflect, dct=mel_dct(n_ceps, n_mels),
                           lifter=mel_lifter_kaldi(n_ceps, cepstral_lifter), energy=bool(use_energy), energy_scale=float(scale) ** 2,
-                          energy_floor=energy_floor)
+                          energy_floor=energy_floor, reflect_edges=bool(_reflect))
+
+    @classmethod
+    def mfcc_reflected(cls, ctx, *args, **kw):
+        """Kaldi's MFCC with --snip-edges=false: MelSpec.mfcc's arguments, defaults and tables, word for word, on MelSpec.kaldi_reflected's
+        frames (its docstring has the placement, the count, what the reflection is about and how to get a whole utterance's
+        features from read_mel).  With use_energy the frame's log energy is taken over the reflected, mean-removed frame.  dither,
+        vtln_warp, htk_compat and raw_energy=False are refused by name as for MelSpec.mfcc (snip_edges, if given, must be False).  What
+        an outside implementation has and has not checked is as for MelSpec.kaldi_reflected and MelSpec.mfcc together."""
+        if "_reflect" in kw:
+            raise TypeError("MelSpec.mfcc_reflected: unknown argument '_reflect'")
+        return cls.mfcc(ctx, *args, _reflect=True, **kw)
 
     def window_len(self, n_frames):
         """The samples that n_frames frames span: (n_frames - 1) * hop + n_fft (0 for no frame; win_length in place of n_fft for a
         framed spec); n_frames * hop for a centred spec (torch.stft gives 1 + L // hop frames on such a window; read_mel takes the
-        first n_frames)."""
+        first n_frames) and for a reflected spec (whose frame t is centred on sample t * hop + hop // 2)."""
         if int(n_frames) <= 0:
             return 0
-        return int(n_frames) * self.hop if self.center else (int(n_frames) - 1) * self.hop + self.win_length
+        return int(n_frames) * self.hop if self.center or self.reflect_edges else (int(n_frames) - 1) * self.hop + self.win_length
 
     def valid_frames(self, valid, n_frames):
         """valid_frames of windows with `valid` samples inside their streams (int64 array): min(ceil(valid / hop), n_frames), and
         for a centred spec 0 where valid == 0, else min(ceil((valid + n_fft // 2) / hop), n_frames).  A spec that counts whole
-        frames: 0 where valid < win_length, else min(1 + (valid - win_length) // hop, n_frames)."""
+        frames: 0 where valid < win_length, else min(1 + (valid - win_length) // hop, n_frames).  A reflected spec:
+        min((valid + hop // 2) // hop, n_frames)."""
         v = np.asarray(valid, dtype=np.int64)
+        if self.reflect_edges:
+            return np.minimum((v + self.hop // 2) // self.hop, int(n_frames)).astype(np.int64)
         if self.whole_frames:
             return np.where(v < self.win_length, 0, np.minimum(1 + (v - self.win_length) // self.hop, int(n_frames))).astype(np.int64)
         P = self.n_fft // 2 if self.center else 0
@@ -1977,7 +2036,12 @@ class StreamSet:
         one clx_mel_windows call on that [B, L] batch, with L = spec.window_len(n_frames): (n_frames - 1) * hop + n_fft, and for a
         centred spec `length` or n_frames * hop (the crop the frames are centred on and reflected at; it must be longer than
         n_fft // 2 and hold the frames: (n_frames - 1) * hop + n_fft <= length + 2 * (n_fft // 2)).  For an uncentred spec `length`
-        must be None or that L.  Returns (float32 tensor on the context's GPU: [B, n_out, n_frames] for layout "ct",
+        must be None or that L -- unless the spec is reflected (MelSpec.kaldi_reflected, MelSpec.mfcc_reflected, reflect_edges=True):
+        then L is `length`, any whole number from 0 up, or n_frames * hop.  A reflected spec's frames are reflected about the crop
+        [starts[k], starts[k] + valid[k]), valid[k] being the part of the L samples inside the stream, and never reach the stream's
+        samples outside it.  Kaldi's snip_edges=false features of a whole utterance of T samples therefore need starts[k] = 0,
+        n_frames >= (T + hop // 2) // hop and length >= T: the default length n_frames * hop can be shorter than T, and the crop would
+        then be cut there and reflected early.  Returns (float32 tensor on the context's GPU: [B, n_out, n_frames] for layout "ct",
         [B, n_frames, n_out] for "tc", n_out = spec.n_out: n_mels, or n_ceps of a cepstral spec; valid_frames): valid_frames[k] (int64 tensor) = spec.valid_frames(valid[k], n_frames) with
         valid[k] the window's samples inside its stream; a frame from there on is zeros, whatever the mode -- the scaled silence value
         for a spec with top.  The launches are queued behind read()'s, on the stream read() uses (gather_windows has the rule).
@@ -1999,7 +2063,7 @@ class StreamSet:
         if length is not None:
             if isinstance(length, bool) or int(length) != length or int(length) < 0:
                 raise ValueError("read_mel: length must be a whole number, not negative")
-            if not spec.center and int(length) != L:
+            if not spec.center and not spec.reflect_edges and int(length) != L:
                 raise ValueError("read_mel: length must be None or %d ((n_frames - 1) * hop + n_fft) for a spec that is not centred, not %r" % (L, length))
             L = int(length)
         if spec.center and n_frames > 0:

@@ -1587,16 +1587,19 @@ extern "C" int clx_mel_create(clx_ctx* ctx, uint32_t n_fft, uint32_t hop, const 
     return clx_mel_create_ex(ctx, n_fft, hop, window, fbank, n_mels, mode, floor, nullptr, spec);
 }
 
-// clx_mel_create_ex, clx_mel_create_framed and (cepstral) clx_mel_create_cepstral: the tables of any of them, uploaded
+// clx_mel_create_ex, clx_mel_create_framed, (cepstral) clx_mel_create_cepstral and (reflected) clx_mel_create_reflected: the tables of
+// any of them, uploaded
 static int clx_mel_create_any(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank,
                               uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_opts* opts,
-                              const clx_mel_frame_opts* fopts, clx_mel_spec** spec, bool cepstral = false, const clx_mel_cep_opts* qopts = nullptr) {
+                              const clx_mel_frame_opts* fopts, clx_mel_spec** spec, bool cepstral = false, const clx_mel_cep_opts* qopts = nullptr,
+                              bool reflected = false) {
     if (!ctx) return CLX_API_ERROR;
     if (!spec) { ctx->last_error = "clx_mel_create: null argument"; return CLX_API_ERROR; }
     *spec = nullptr;
     clx_mel_spec* sp = new (std::nothrow) clx_mel_spec();
     if (!sp) { ctx->last_error = "clx_mel_create: out of memory"; return CLX_API_ERROR; }
-    const std::string why = cepstral ? clx_mel_build_cepstral(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, fopts, qopts)
+    const std::string why = reflected ? clx_mel_build_reflected(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, fopts, qopts) :
+                            cepstral ? clx_mel_build_cepstral(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, fopts, qopts)
                                      : clx_mel_build_framed(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, &sp->t, opts, fopts);
     if (!why.empty()) { delete sp; ctx->last_error = why; return CLX_API_ERROR; }
     sp->ctx = ctx;
@@ -1636,6 +1639,12 @@ extern "C" int clx_mel_create_cepstral(clx_ctx* ctx, uint32_t n_fft, uint32_t wi
     return clx_mel_create_any(ctx, n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, nullptr, opts, spec, true, cep);
 }
 
+extern "C" int clx_mel_create_reflected(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank,
+                                        uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor, const clx_mel_frame_opts* opts,
+                                        const clx_mel_cep_opts* cep, clx_mel_spec** spec) {
+    return clx_mel_create_any(ctx, n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, nullptr, opts, spec, cep != nullptr, cep, true);
+}
+
 extern "C" void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec) {
     if (!ctx || !spec) return;
     auto it = std::find(ctx->mel_specs.begin(), ctx->mel_specs.end(), spec);
@@ -1659,8 +1668,8 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
     if (!ctx->ev_mel_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_up, hipEventDisableTiming));
     if (!ctx->ev_mel_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_done, hipEventDisableTiming));
-    const bool is_c = clx_mel_is_c(spec->t);
-    const size_t words = is_c ? 3u * n_windows : n_windows;   // (valid_frames; centred or ranged: also lim and wmax)
+    const bool is_c = clx_mel_is_c(spec->t), is_r = clx_mel_is_r(spec->t);
+    const size_t words = is_c ? 3u * n_windows : is_r ? 2u * n_windows : n_windows;   // (valid_frames; centred or ranged: also lim and wmax; reflected: also vlen)
     if (words > ctx->mel_cap) {                                // a larger table, before anything is queued; the old one is not freed here
         const size_t want = words + words / 2 + 64;
         uint32_t* d = nullptr; uint32_t* h = nullptr;
@@ -1673,11 +1682,20 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
         HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_mel_done, 0));
     }
     if (is_c) clx_mel_fill_c(ctx->h_mel, valid, n_windows, spec->t, window_len, n_frames);
+    else if (is_r) clx_mel_fill_r(ctx->h_mel, valid, n_windows, spec->t, n_frames);
     else clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames, 0u, clx_mel_whole(spec->t));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_up, stream));
     ctx->mel_used = true;                                      // (from here on the staging and the table are in use)
-    if (clx_mel_is_q(spec->t)) {
+    if (is_r && clx_mel_is_q(spec->t)) {
+        hipLaunchKernelGGL(clx_k_mel_qr, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                           (const uint32_t*)ctx->d_mel, (uint32_t)n_windows, spec->dev, clx_mel_fargs(spec->t), spec->qdev, clx_mel_origin(spec->t),
+                           n_groups, window_len, n_frames, layout, (float*)d_out);
+    } else if (is_r) {
+        hipLaunchKernelGGL(clx_k_mel_fr, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
+                           (const uint32_t*)ctx->d_mel, (uint32_t)n_windows, spec->dev, clx_mel_fargs(spec->t), clx_mel_origin(spec->t), n_groups,
+                           window_len, n_frames, layout, (float*)d_out);
+    } else if (clx_mel_is_q(spec->t)) {
         hipLaunchKernelGGL(clx_k_mel_q, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
                            (const uint32_t*)ctx->d_mel, spec->dev, clx_mel_fargs(spec->t), spec->qdev, n_groups, window_len, n_frames, layout,
                            (float*)d_out);

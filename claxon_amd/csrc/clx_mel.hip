@@ -62,6 +62,15 @@
 // fmaf chain, m ascending, the dct row from global memory (it is a few KiB and stays in the caches), and applies the lifter or
 // takes the energy.  One pass only: a cepstral spec has n_bins <= 256, for a cepstral output has no rows to park partial band sums in.
 //
+// clx_k_mel_fr and clx_k_mel_qr are the reflected forms of those two (claxon_hip.h, clx_mel_create_reflected), which is
+// Kaldi's snip_edges=false: frame t's tap n is index t * H + H / 2 - Nw / 2 + n of the window's valid[k] samples continued on both sides
+// by reflection with the edge sample repeated, as often as it takes.  They differ from clx_k_mel_f / clx_k_mel_q in the loads alone: the
+// prologue's sums, the energy pass and the two staged loads with their two pre-emphasis neighbours.  A block whose live frames lie
+// wholly inside [0, valid[k]) -- all but the first and last group or two of a window -- is told so once, before the pass loop, by a
+// block-uniform flag, and addresses its taps directly as clx_k_mel_f does; an edge block sends each tap through clx_mel::rtap, where a
+// tap inside [0, valid[k]) costs one 64-bit compare and a tap outside is folded with 32-bit arithmetic (the distance past the edge is
+// at most win_length / 2 + 1).  The call's table is vframes[B] then vlen[B] = valid[k]; the origin H / 2 - Nw / 2 is a kernel argument.
+//
 // clx_mel_build / clx_mel_build_framed / clx_mel_build_cepstral / clx_mel_check / clx_mel_fill / clx_mel_fill_c are the host side (plain C++, shared with the
 // wave simulator).
 #include <hip/hip_runtime.h>
@@ -115,6 +124,7 @@ struct clx_mel_tables {
     float preemph = 0.f;
     uint32_t n_ceps = 0, has_lifter = 0, energy = 0;         // clx_mel_create_cepstral: clx_mel_cep_opts (n_ceps == 0: not cepstral)
     float energy_scale = 1.f, energy_floor = 0.f;
+    uint32_t reflect = 0;                                    // clx_mel_create_reflected
     std::vector<float> dct, lifter;
     std::vector<float> basis, fbank;
     std::vector<uint32_t> ends;
@@ -186,6 +196,25 @@ __device__ __forceinline__ float tap(const float* a, int64_t i, uint32_t L, uint
     return (uint64_t)i < (uint64_t)lim ? a[i] : 0.f;
 }
 
+// The index map of a reflected frame (clx_k_mel_fr, clx_k_mel_qr): sample r(i) of a window of V >= 1 valid samples, r being Kaldi's
+// loop -- while i is outside [0, V): i = -i - 1 below 0, i = 2 V - 1 - i from V up.  A tap inside costs the compare.  Outside, e is
+// the distance past the edge (0: the edge sample's first repeat); the live frames of a window keep it to win_length / 2 + 1 at most,
+// so it is taken as 32 bits: e < V is one reflection, else e mod 2 V says how far into which image of the window the tap lies (2 V
+// fits 32 bits there, V being at most e).  Whatever i is, the float loaded is one of a[0 .. V).
+__device__ __forceinline__ float rtap(const float* a, int64_t i, uint32_t V) {
+    if ((uint64_t)i >= (uint64_t)V) {
+        const bool below = i < 0;
+        uint32_t e = (uint32_t)(below ? -i - 1 : i - (int64_t)V);
+        bool flip = !below;                                    // (flip: counted down from V - 1; else up from 0)
+        if (e >= V) {
+            e %= 2u * V;
+            if (e >= V) { e -= V; flip = !flip; }
+        }
+        i = flip ? (int64_t)(V - 1u - e) : (int64_t)e;
+    }
+    return a[i];
+}
+
 // cell c of the block's n_mels x kF cells: lanes run along the layout's output row
 __device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mels, uint32_t* m, uint32_t* f) {
     if (layout == CLX_WINDOW_CT) { *f = c % kF; *m = c / kF; }
@@ -197,12 +226,14 @@ __device__ __forceinline__ void cell(uint32_t c, uint32_t layout, uint32_t n_mel
 // Block b: frame group b % n_groups of window b / n_groups (clx_mel_check gives n_groups).  `audio` is [B, L], vframes[k] =
 // valid_frames[k] <= n_frames, `out` is [B, n_mels, n_frames] (CLX_WINDOW_CT) or [B, n_frames, n_mels] (CLX_WINDOW_TC).  kC: the
 // centred and/or ranged form (X, lim[k] and wmax[k] are used by it alone).  kFr: the conditioning form (F is used by it alone).
-// kQ (with kFr): the cepstral form (Q is used by it alone); `out` has n_ceps in place of n_mels.
+// kQ (with kFr): the cepstral form (Q is used by it alone); `out` has n_ceps in place of n_mels.  kR (with kFr): the reflected form
+// (lim[k] = valid[k] and org = H / 2 - Nw / 2 are used by it alone).
 namespace clx_mel {
-template <bool kC, bool kFr, bool kQ>
+template <bool kC, bool kFr, bool kQ, bool kR = false>
 __device__ __forceinline__ void body(const float* __restrict__ audio, const uint32_t* __restrict__ vframes,
                                      const clx_mel_dev S, const clx_mel_cdev X, const clx_mel_fdev F, const clx_mel_qdev Q, const uint32_t* __restrict__ lim,
-                                     uint32_t* wmax, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout, float* __restrict__ out) {
+                                     uint32_t* wmax, uint32_t n_groups, uint32_t L, uint32_t n_frames, uint32_t layout, float* __restrict__ out,
+                                     int32_t org = 0) {
     __shared__ __attribute__((aligned(16))) float s_stage[kStage];
     const uint32_t tid = threadIdx.x, k = blockIdx.x / n_groups, f0 = (blockIdx.x - k * n_groups) * kF;
     const uint32_t vf = vframes[k];
@@ -243,15 +274,35 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
     float mu0 = 0.f, mu1 = 0.f;
     const float* a0 = a;
     const float* a1 = a;
+    // kR: the window's valid samples, the index of the block's first tap, whether every tap of the block's live frames lies inside
+    // [0, V) (uniform over the block: such a block addresses its taps as clx_k_mel_f does), and the first taps of this lane's two frames
+    uint32_t V = 0u;
+    int64_t g0 = 0, b0 = 0, b1 = 0;
+    bool direct = false;
+    if constexpr (kR) {
+        V = lim[k];
+        g0 = (int64_t)((uint64_t)f0 * S.hop) + (int64_t)org;
+        direct = g0 >= 0 && g0 + (int64_t)((uint64_t)(nf_live - 1u) * S.hop) + (int64_t)S.n_fft <= (int64_t)V;
+        b0 = g0 + (int64_t)((uint64_t)x_f * S.hop);
+        b1 = b0 + (int64_t)(16ull * S.hop);
+    }
     if constexpr (kFr) {
-        a0 = a + (uint64_t)(f0 + x_f) * S.hop;
-        a1 = a + (uint64_t)(f0 + x_f + 16u) * S.hop;
+        if constexpr (!kR) {
+            a0 = a + (uint64_t)(f0 + x_f) * S.hop;
+            a1 = a + (uint64_t)(f0 + x_f + 16u) * S.hop;
+        }
         if (F.remove_dc) {                                     // (uniform over the block)
             const uint32_t sf = tid >> 3;                      // lanes 8 sf .. 8 sf + 7 sum frame sf
             float sum = 0.f;
             if (sf < nf_live) {
-                const float* const fr = a + (uint64_t)(f0 + sf) * S.hop;
-                for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) sum = add_rn(sum, fr[n]);
+                if constexpr (kR) {
+                    const int64_t b = g0 + (int64_t)((uint64_t)sf * S.hop);
+                    if (direct) for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) sum = add_rn(sum, a[b + n]);
+                    else for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) sum = add_rn(sum, rtap(a, b + n, V));
+                } else {
+                    const float* const fr = a + (uint64_t)(f0 + sf) * S.hop;
+                    for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) sum = add_rn(sum, fr[n]);
+                }
             }
             sum = add_rn(sum, __shfl_xor(sum, 4));
             sum = add_rn(sum, __shfl_xor(sum, 2));
@@ -269,11 +320,20 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
             const uint32_t sf = tid >> 3;
             float e = 0.f;
             if (sf < nf_live) {
-                const float* const fr = a + (uint64_t)(f0 + sf) * S.hop;
                 const float mu = F.remove_dc ? s_stage[sf] : 0.f;   // (as mu0 and mu1: read before the first round's barrier)
-                for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) {
-                    const float d = F.remove_dc ? sub_rn(fr[n], mu) : fr[n];
-                    e = fmaf(d, d, e);
+                if constexpr (kR) {
+                    const int64_t b = g0 + (int64_t)((uint64_t)sf * S.hop);
+                    for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) {
+                        const float x = direct ? a[b + n] : rtap(a, b + n, V);
+                        const float d = F.remove_dc ? sub_rn(x, mu) : x;
+                        e = fmaf(d, d, e);
+                    }
+                } else {
+                    const float* const fr = a + (uint64_t)(f0 + sf) * S.hop;
+                    for (uint32_t n = tid & 7u; n < S.n_fft; n += 8u) {
+                        const float d = F.remove_dc ? sub_rn(fr[n], mu) : fr[n];
+                        e = fmaf(d, d, e);
+                    }
                 }
             }
             e = add_rn(e, __shfl_xor(e, 4));
@@ -312,6 +372,15 @@ __device__ __forceinline__ void body(const float* __restrict__ audio, const uint
                     if constexpr (kC) {
                         if (x_f < nf_live) px0 = tap(a, i0 + (int64_t)(s * kKS), L, lm, X.zero);
                         if (x_f + 16u < nf_live) px1 = tap(a, i1 + (int64_t)(s * kKS), L, lm, X.zero);
+                    } else if constexpr (kR) {
+                        const uint32_t nb = n ? n - 1u : 0u;   // (the first tap refers to the frame's own first tap, mapped as it is)
+                        if (direct) {
+                            if (x_f < nf_live) { px0 = a[b0 + n]; if (F.preemph > 0.f) pv0 = a[b0 + nb]; }
+                            if (x_f + 16u < nf_live) { px1 = a[b1 + n]; if (F.preemph > 0.f) pv1 = a[b1 + nb]; }
+                        } else {
+                            if (x_f < nf_live) { px0 = rtap(a, b0 + n, V); if (F.preemph > 0.f) pv0 = rtap(a, b0 + nb, V); }
+                            if (x_f + 16u < nf_live) { px1 = rtap(a, b1 + n, V); if (F.preemph > 0.f) pv1 = rtap(a, b1 + nb, V); }
+                        }
                     } else if constexpr (kFr) {
                         const uint32_t nb = n ? n - 1u : 0u;   // (the first tap refers to the frame's own first sample)
                         if (x_f < nf_live) { px0 = a0[n]; if (F.preemph > 0.f) pv0 = a0[nb]; }
@@ -489,6 +558,20 @@ extern "C" __global__ __launch_bounds__(256) void clx_k_mel_q(const float* __res
     clx_mel::body<false, true, true>(audio, vframes, S, clx_mel_cdev(), F, Q, nullptr, nullptr, n_groups, L, n_frames, layout, out);
 }
 
+// The reflected forms of the two (every reflected spec runs one of them, whether it conditions or not).  `table` is the call's device
+// table: vframes[B], then vlen[B] = valid[k], the samples a tap is reflected about and loaded from; org = hop / 2 - win_length / 2.
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel_fr(const float* __restrict__ audio, const uint32_t* __restrict__ table, uint32_t n_windows,
+                                                               clx_mel_dev S, clx_mel_fdev F, int32_t org, uint32_t n_groups, uint32_t L, uint32_t n_frames,
+                                                               uint32_t layout, float* __restrict__ out) {
+    clx_mel::body<false, true, false, true>(audio, table, S, clx_mel_cdev(), F, clx_mel_qdev(), table + n_windows, nullptr, n_groups, L, n_frames, layout, out, org);
+}
+
+extern "C" __global__ __launch_bounds__(256) void clx_k_mel_qr(const float* __restrict__ audio, const uint32_t* __restrict__ table, uint32_t n_windows,
+                                                               clx_mel_dev S, clx_mel_fdev F, clx_mel_qdev Q, int32_t org, uint32_t n_groups, uint32_t L,
+                                                               uint32_t n_frames, uint32_t layout, float* __restrict__ out) {
+    clx_mel::body<false, true, true, true>(audio, table, S, clx_mel_cdev(), F, Q, table + n_windows, nullptr, n_groups, L, n_frames, layout, out, org);
+}
+
 // The centred and/or ranged form.  `table` is the call's device table: vframes[B], then lim[B] (the end of what a tap may load of
 // window k: valid[k] in zero mode, L otherwise), then wmax[B] (ranged: enc(-inf) on entry, the encoded maximum of window k's cells
 // when the launch has finished).
@@ -619,10 +702,24 @@ inline std::string clx_mel_build(uint32_t n_fft, uint32_t hop, const float* wind
     return clx_mel_build_framed(n_fft, n_fft, hop, window, fbank, n_fft / 2u + 1u, n_mels, mode, floor, t, opts, nullptr);
 }
 
+// The host side of clx_mel_create_reflected: the framed spec's checks and tables, or the cepstral spec's when `q` is given, and the
+// refusal of whole_frames (a reflected spec has a count rule of its own).
+inline std::string clx_mel_build_reflected(uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window, const float* fbank, uint32_t n_bins,
+                                           uint32_t n_mels, uint32_t mode, float floor, clx_mel_tables* t, const clx_mel_frame_opts* fopts,
+                                           const clx_mel_cep_opts* q) {
+    const std::string why = q ? clx_mel_build_cepstral(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, t, fopts, q)
+                              : clx_mel_build_framed(n_fft, win_length, hop, window, fbank, n_bins, n_mels, mode, floor, t, nullptr, fopts);
+    if (!why.empty()) return why;
+    if (fopts && fopts->whole_frames != 0u) return "clx_mel_create_reflected: whole_frames must be 0, a reflected spec counts (valid + hop / 2) / hop frames";
+    t->reflect = 1u;
+    return std::string();
+}
+
 // The host side of clx_mel_windows: checks the arguments (nullptr: fine, else the text for clx_last_error) and gives the launch
 // shape: *n_groups frame groups per window (0: nothing to launch), n_windows * *n_groups blocks of clx_mel::kThreads.  A centred
 // spec is held to torch.stft's frame count (P = n_fft / 2 < window_len, and the last frame ends inside window_len + 2 P), any other
-// to (n_frames - 1) * hop + win_length <= window_len (win_length = n_fft unless the spec is framed); a ranged
+// to (n_frames - 1) * hop + win_length <= window_len (win_length = n_fft unless the spec is framed), except a reflected spec, which
+// is held to valid[k] <= window_len alone; a ranged
 // one also gets *n_tiles, the tiles per window of clx_k_mel_range (n_windows * *n_tiles blocks).
 inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, size_t n_windows, uint32_t window_len, const uint32_t* valid,
                                  uint32_t n_frames, uint32_t layout, const void* out, uint32_t* n_groups, uint32_t* n_tiles = nullptr) {
@@ -636,7 +733,7 @@ inline const char* clx_mel_check(const clx_mel_tables* t, const void* audio, siz
         const uint64_t P = t->n_fft / 2u;
         if (P >= window_len) return "clx_mel_windows: a centred spec needs n_fft / 2 less than window_len";
         if ((uint64_t)window_len + 2u * P < (uint64_t)(n_frames - 1u) * t->hop + t->n_fft) return "clx_mel_windows: window_len + 2 * (n_fft / 2) is less than (n_frames - 1) * hop + n_fft";
-    } else if ((uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->win)
+    } else if (!t->reflect && (uint64_t)window_len < (uint64_t)(n_frames - 1u) * t->hop + t->win)
         return t->win == t->n_fft ? "clx_mel_windows: window_len is less than (n_frames - 1) * hop + n_fft"
                                   : "clx_mel_windows: window_len is less than (n_frames - 1) * hop + win_length";
     for (size_t k = 0; k < n_windows; ++k)
@@ -662,6 +759,21 @@ inline void clx_mel_fill(uint32_t* vframes, const uint32_t* valid, size_t n_wind
         if (whole_win) v = valid[k] < whole_win ? 0u : 1u + (uint64_t)(valid[k] - whole_win) / hop;
         else v = valid[k] ? ((uint64_t)valid[k] + P + hop - 1u) / hop : 0u;
         vframes[k] = v < n_frames ? (uint32_t)v : n_frames;
+    }
+}
+
+// clx_k_mel_fr / clx_k_mel_qr run a reflected spec
+inline bool clx_mel_is_r(const clx_mel_tables& t) { return t.reflect != 0u; }
+
+// (their origin: the index of frame 0's tap 0)
+inline int32_t clx_mel_origin(const clx_mel_tables& t) { return (int32_t)(t.hop / 2u) - (int32_t)(t.win / 2u); }
+
+// their table, 2 * n_windows words: valid_frames[k] = min(n_frames, (valid[k] + hop / 2) / hop), then vlen[k] = valid[k]
+inline void clx_mel_fill_r(uint32_t* table, const uint32_t* valid, size_t n_windows, const clx_mel_tables& t, uint32_t n_frames) {
+    for (size_t k = 0; k < n_windows; ++k) {
+        const uint64_t v = ((uint64_t)valid[k] + t.hop / 2u) / t.hop;
+        table[k] = v < n_frames ? (uint32_t)v : n_frames;
+        table[n_windows + k] = valid[k];
     }
 }
 

@@ -584,6 +584,37 @@ typedef struct { uint32_t n_ceps; const float* dct /*[n_ceps][n_mels]*/; const f
 int  clx_mel_create_cepstral(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window /*[win_length]*/,
                              const float* fbank /*[n_mels][n_bins]*/, uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor,
                              const clx_mel_frame_opts* opts, const clx_mel_cep_opts* cep, clx_mel_spec** spec);
+/* Reflected specs: Kaldi's snip_edges=false (feature-window.cc: NumFrames and ExtractWindow, restated), which lhotse's extractors and
+ * icefall's kaldifeat set-ups use, so that an utterance of T samples has (T + hop/2) / hop frames whatever the frame length is
+ * (clx_k_mel_fr, clx_k_mel_qr).  A reflected spec is clx_mel_create_framed's spec, or with cep != NULL
+ * clx_mel_create_cepstral's: the same arguments, tables, conditioning, basis, band sums, logarithm, DCT, lifter and raw-energy row,
+ * word for word.  Three things differ.  Below V = valid[k], H = hop, Nw = win_length, and every division is the integer division of
+ * non-negative numbers.
+ *
+ *   count      window k has valid_frames[k] = min(n_frames, (V + H/2) / H) live frames: none for V = 0, none for 0 < V < H - H/2.
+ *              whole_frames does not apply and must be 0.
+ *   placement  tap n of frame t is index i = t*H + H/2 - Nw/2 + n of the window, a signed 64-bit number: negative for the first
+ *              frames when Nw > H, and from V up for the last ones.
+ *   edge rule  the tap's value is x[n] = a[k][r(i)], r being Kaldi's loop: while i < 0 or i >= V, i = -i - 1 if i < 0, else
+ *              i = 2V - 1 - i.  This is reflection with the edge sample repeated (.. a[1] a[0] | a[0] a[1] .. a[V-1] | a[V-1]
+ *              a[V-2] ..), iterated, so that a window shorter than a frame is folded as often as it takes; equivalently
+ *              j = i mod 2V (non-negative) and r = j < V ? j : 2V - 1 - j.  The reflection is about V and not about window_len, and
+ *              no float outside [0, V) of a window is read.
+ *
+ * Everything behind it sees the frame x[n] = a[k][r(i_n)]: the mean is summed in the stated lane order (lane i of 8 adds n = i,
+ * i+8, .., then the partial sums are folded 4, 2, 1); the pre-emphasis tap is x[n-1], the mapped neighbour, and x[0] itself for
+ * n = 0; the raw energy of a cepstral spec is taken over the mapped, mean-removed frame.  A dead frame is +0.0 in every row and is
+ * not computed; the call writes all of d_out.  clx_mel_windows puts no condition between window_len and n_frames on a reflected
+ * spec: valid[k] <= window_len is all.  Hence: the reflected spec's live cells of window k are, word for word, the cells of the
+ * whole-frame spec with the same tables on the window p[i] = a[k][r(i + H/2 - Nw/2)], i < (T-1)*H + Nw, T the live frame count.
+ *
+ * Every reflected spec runs clx_k_mel_fr, or clx_k_mel_qr if it is cepstral, whether it conditions its frames or not; the limits
+ * are the siblings' (a cepstral one: n_mels <= 128, n_bins <= 256).  CLX_API_ERROR, each by a text of its own, for every refusal of
+ * clx_mel_create_framed, with cep != NULL every refusal of clx_mel_create_cepstral, and for opts->whole_frames != 0.  The count
+ * and the origin H/2 - Nw/2 restate Kaldi's code; they have not been compared with a Kaldi binary or another implementation. */
+int  clx_mel_create_reflected(clx_ctx* ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float* window /*[win_length]*/,
+                              const float* fbank /*[n_mels][n_bins]*/, uint32_t n_bins, uint32_t n_mels, uint32_t mode, float floor,
+                              const clx_mel_frame_opts* opts, const clx_mel_cep_opts* cep /* NULL: fbank rows */, clx_mel_spec** spec);
 void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
 /* The features of d_audio [n_windows][window_len] (device, float32) into d_out (device, float32), asynchronously on `stream`
  * (NULL: the context's).  valid is a host array; it is staged like the window table of clx_gather_windows: pinned staging, a
@@ -594,7 +625,8 @@ void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec);
  * centred or ranged spec runs clx_k_mel_c (its table also carries, per window, the end of what may be loaded and the encoded
  * maximum, initialised by the upload), a ranged one clx_k_mel_range behind it; a framed spec is held to win_length in place of
  * n_fft and to its own valid_frames rule, and runs clx_k_mel_f if it conditions its frames; a cepstral spec is a framed spec that
- * runs clx_k_mel_q and writes n_ceps rows in place of n_mels. */
+ * runs clx_k_mel_q and writes n_ceps rows in place of n_mels; a reflected spec is held to valid[k] <= window_len alone and to its
+ * own count, runs clx_k_mel_fr or (cepstral) clx_k_mel_qr, and its table also carries valid[k] per window. */
 int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio, size_t n_windows, uint32_t window_len,
                      const uint32_t* valid, uint32_t n_frames, uint32_t layout, void* d_out, void* stream);
 /* Per-window mean and variance normalisation of a dense float32 batch, in place on the device: what wav2vec 2.0 / HuBERT / WavLM do
