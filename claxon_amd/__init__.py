@@ -102,13 +102,13 @@ EXPORTS = [
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
-    "clx_norm_windows",
+    "clx_norm_windows", "clx_add_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -196,6 +196,7 @@ def lib():
     L.clx_mel_destroy.restype = None
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_norm_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+    L.clx_add_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -781,6 +782,56 @@ class Context:
         opts = norm._opts()
         self._check(lib().clx_norm_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), int(layout), C.byref(opts), s_ptr,
                                            C.c_void_p(handle) if handle else None))
+        return data
+
+    def add_windows(self, data, valid, noise, noise_valid, noise_index, snr_db, layout, gains=None, stream=None):
+        """clx_add_windows: the windows of `noise` -- [N, rows, T] (WINDOW_CT) or [N, T, rows] (WINDOW_TC) -- added in place to the
+        dense float32 batch `data` ([B, rows, T] / [B, T, rows], rows 1..8) at a signal-to-noise ratio: window k gets noise window
+        noise_index[k] (-1: none) times the gain that puts the mean power of the signal's valid[k] live samples snr_db[k] dB above
+        that of the noise samples inside them (claxon_hip.h has the definition and the order of the sums); snr_db is a scalar or
+        one value per window.  Padding and the cells behind the noise's end keep their words; `noise` is not written.  `gains`, if
+        given, is a [B] float32 tensor that receives every window's gain.  `data`, `noise` and `gains` are CUDA float32 tensors,
+        or `data` is a (pointer, B, rows, T) tuple, `noise` a (pointer, N) pair and `gains` a pointer.  Asynchronous on `stream` as
+        gather_windows is.  Returns `data`."""
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("add_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        if hasattr(noise, "data_ptr"):
+            if noise.dim() != 3 or not noise.is_contiguous() or str(noise.dtype) != "torch.float32" \
+                    or tuple(noise.shape[1:]) != ((T, rows) if tc else (rows, T)):
+                raise ValueError("add_windows: noise must be a contiguous float32 [N, rows, T] or [N, T, rows] tensor with data's rows and T")
+            n_ptr, N = noise.data_ptr(), int(noise.shape[0])
+        elif noise is None:
+            n_ptr, N = None, 0
+        else:
+            n_ptr, N = (int(noise[0]) if noise[0] else None), int(noise[1])
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        noise_valid = np.ascontiguousarray(noise_valid, dtype=np.uint32).reshape(-1)
+        noise_index = np.ascontiguousarray(noise_index, dtype=np.int32).reshape(-1)
+        snr = np.ascontiguousarray(snr_db, dtype=np.float32).reshape(-1)
+        if snr.size == 1 and B != 1:
+            snr = np.full(B, snr[0], dtype=np.float32)
+        for name, a, want in (("valid", valid, B), ("noise_index", noise_index, B), ("snr_db", snr, B), ("noise_valid", noise_valid, N)):
+            if a.size != want:
+                raise ValueError("add_windows: %s has %d entries for %d windows" % (name, a.size, want))
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("add_windows: %s is out of range" % name)
+        if hasattr(gains, "data_ptr"):
+            if tuple(gains.shape) != (B,) or not gains.is_contiguous() or str(gains.dtype) != "torch.float32":
+                raise ValueError("add_windows: gains must be a contiguous float32 [B] tensor")
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        g_ptr = gains.data_ptr() if hasattr(gains, "data_ptr") else (int(gains) if gains else None)
+        self._check(lib().clx_add_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), n_ptr, N, _np_ptr(noise_valid), _np_ptr(noise_index),
+                                          _np_ptr(snr), int(layout), None, g_ptr, C.c_void_p(handle) if handle else None))
         return data
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -1807,6 +1858,67 @@ class Norm:
         return hash((self.mean, self.var, self.ddof, self.eps, self.pad))
 
 
+# ---- a second recording behind the windows ----------------------------------------------------------------------------------------
+
+class Add:
+    """What read(..., add=) and read_mel(..., add=) mix into their windows (clx_add_windows, claxon_hip.h): window k receives the
+    samples of stream stream_ids[k] of `source` from sample starts[k] on (counted as read() counts them, at the call's sample
+    rate), scaled so that the window's mean power over its valid samples lies snr_db[k] dB above the mean power of the noise
+    samples inside them.  `source` is a StreamSet of the reading set's context, None the reading set itself; a stream id of -1
+    gives that window no noise; snr_db is a scalar or one value per window, finite within -200 .. 200 or +inf (nothing added).
+    A noise stream that ends inside the window is added as far as it goes and counted over that part only; it is not repeated.
+    A plain value: it owns nothing on the device.  ValueError for arrays that differ in length, an id below -1, a negative start
+    and a snr_db that is NaN, -inf or beyond 200 in magnitude; the read refuses lengths that differ from its own, an id the source
+    does not have, a closed source and a source of another context."""
+
+    def __init__(self, stream_ids, starts, snr_db, source=None):
+        if source is not None and not isinstance(source, StreamSet):
+            raise ValueError("Add: source must be a StreamSet or None, not %r" % (source,))
+        self.stream_ids = np.array(stream_ids, dtype=np.int64).reshape(-1)
+        self.starts = np.array(starts, dtype=np.int64).reshape(-1)
+        if self.stream_ids.size != self.starts.size:
+            raise ValueError("Add: stream_ids and starts differ in length")
+        snr = np.array(snr_db, dtype=np.float32)
+        if snr.ndim == 0:
+            snr = np.full(self.stream_ids.size, snr, dtype=np.float32)
+        self.snr_db = snr.reshape(-1)
+        if self.snr_db.size != self.stream_ids.size:
+            raise ValueError("Add: snr_db must be a scalar or one value per window")
+        if self.stream_ids.size and self.stream_ids.min() < -1:
+            raise ValueError("Add: a stream id is below -1")
+        if np.any((self.starts < 0) & (self.stream_ids >= 0)):
+            raise ValueError("Add: a noise window starts before its stream")
+        if np.any(np.isnan(self.snr_db) | (np.isinf(self.snr_db) & (self.snr_db < 0)) | (np.isfinite(self.snr_db) & (np.abs(self.snr_db) > 200))):
+            raise ValueError("Add: snr_db must be within -200 .. 200, or +inf")
+        self.source = source
+
+    def __len__(self):
+        return int(self.stream_ids.size)
+
+    def __repr__(self):
+        return "Add(%d windows, %d with noise, source=%s)" % (len(self), int((self.stream_ids >= 0).sum()), "None" if self.source is None else "StreamSet")
+
+    def _plan(self, reader, B, ch, channels, who):
+        """The refusals of a read of B windows with `ch` channels: (source, the windows with noise)."""
+        src = reader if self.source is None else self.source
+        if src._descs is None:
+            raise ValueError("%s: add's source is closed" % who)
+        if src.ctx is not reader.ctx:
+            raise ValueError("%s: add's source belongs to another context" % who)
+        if len(self) != B:
+            raise ValueError("%s: add has %d windows, the call %d" % (who, len(self), B))
+        sel = np.nonzero(self.stream_ids >= 0)[0]
+        if sel.size and self.stream_ids.max() >= len(src):
+            raise ValueError("%s: add names a stream its source does not have" % who)
+        if channels is None:
+            for k in sel.tolist():
+                s = int(self.stream_ids[k])
+                if src.problems[s] is None and src.channels[s] != ch:
+                    raise ValueError("%s: noise stream %d has %d channels, the windows %d (window %d); channels= brings them together"
+                                     % (who, s, src.channels[s], ch, k))
+        return src, sel
+
+
 # ---- sample windows from resident streams -----------------------------------------------------------------------------------------
 
 _LAYOUTS = {"tc": WINDOW_TC, "ct": WINDOW_CT}
@@ -1899,7 +2011,7 @@ class StreamSet:
                 out[s] = (int(self._lengths[s]) * n + o - 1) // o
         return torch.from_numpy(out)
 
-    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None, normalize=None):
+    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None, normalize=None, add=None, return_gains=False):
         """A batch of windows: window k is samples [starts[k], starts[k] + length) of stream stream_ids[k], positions counted as load()
         counts them (by cumulative block size in frame order; the frame headers' sample numbers are not consulted).  Returns (float32
         tensor on the context's GPU, contiguous: [B, length, C] for layout "tc", [B, C, length] for "ct"; valid): valid[k] =
@@ -1930,9 +2042,21 @@ class StreamSet:
 
         With normalize=Norm(...) every window is then normalised per channel over its valid[k] samples (after resampling and
         channels=): one clx_norm_windows call on the result, queued behind the launch that cut the windows; the samples from valid[k]
-        on become the Norm's pad.  The return value is the same pair.  ValueError for a normalize that is not a Norm."""
+        on become the Norm's pad.  The return value is the same pair.  ValueError for a normalize that is not a Norm.
+
+        With add=Add(...) a second recording is mixed into every window at a signal-to-noise ratio, before normalize=: a second
+        read() on the Add's source (this set when it names none) for the windows whose noise stream id is not -1, with this call's
+        length, layout, sample_rate and channels -- the source's frames_decoded counts its frames --, then one clx_add_windows call
+        behind both (claxon_hip.h has the gain: the ratio of mean powers over each side's live samples).  valid is the signal's; a
+        noise stream that ends inside a window is added as far as it goes.  With channels=None the noise streams must have the
+        windows' channel count.  return_gains=True appends the windows' gains (float32 [B] on the GPU, 0 where nothing was added) to
+        the return value.  ValueError for an add that is not an Add, whose length is not this call's, that names a stream its
+        source does not have, or whose source is closed or of another context.  Tiling a short noise over a long window, several
+        Adds in one call and other gain rules are not offered."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read: normalize must be a Norm or None, not %r" % (normalize,))
+        if add is not None and not isinstance(add, Add):
+            raise ValueError("read: add must be an Add or None, not %r" % (add,))
         import torch
         if self._descs is None:
             raise ValueError("read: the stream set is closed")
@@ -1968,6 +2092,8 @@ class StreamSet:
                 k = int(odd[0])
                 raise ValueError("read: no rule brings the %d channels of stream %d to %d (window %d)" % (int(cw[k]), int(sid[k]), ch, k))
         mixed = bool(np.any(cw != ch))                       # (only with channels=K: some window is reduced or replicated)
+        if add is not None:
+            add_src, add_sel = add._plan(self, sid.size, ch, channels, "read")
         B, dev = sid.size, "cuda:%d" % self.ctx.device
         if sample_rate is None:
             valid = np.clip(self._lengths[sid] - st, 0, length)
@@ -1979,7 +2105,7 @@ class StreamSet:
         shape = (B, length, ch) if layout == "tc" else (B, ch, length)
         out = torch.empty(shape, dtype=torch.float32, device=dev)
         if B == 0 or length == 0:
-            return out, torch.from_numpy(valid)
+            return (out, torch.from_numpy(valid)) + ((torch.zeros(B, dtype=torch.float32, device=dev),) if return_gains else ())
         live = np.nonzero(valid > 0)[0]
         # a live window's source span [lo, hi) in its stream's samples: the window itself, or what the filter reaches from it
         lo, hi = st[live], st[live] + valid[live]
@@ -2024,12 +2150,21 @@ class StreamSet:
             else:
                 self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
                                           _LAYOUTS[layout], out)
+        mixing = add is not None and ch > 0 and add_sel.size > 0
+        # the gains: clx_add_windows writes every one of them when it runs, so they need no fill then -- a fill would run on torch's
+        # stream, unordered against the context's own stream that the launches go to when torch's current stream is the default one
+        gains = None if not return_gains else (torch.empty if mixing else torch.zeros)(B, dtype=torch.float32, device=dev)
+        if mixing:
+            noise, noise_valid = add_src.read(add.stream_ids[add_sel], add.starts[add_sel], length, layout, sample_rate=sample_rate, channels=channels)
+            index = np.full(B, -1, dtype=np.int32)
+            index[add_sel] = np.arange(add_sel.size, dtype=np.int32)
+            self.ctx.add_windows(out, valid, noise, noise_valid.numpy(), index, add.snr_db, _LAYOUTS[layout], gains=gains)
         if normalize is not None and ch > 0:
             self.ctx.norm_windows(out, valid, _LAYOUTS[layout], normalize)
-        return out, torch.from_numpy(valid)
+        return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -2048,9 +2183,15 @@ class StreamSet:
 
         With normalize=Norm(...) the features are then normalised per output row over the window's valid_frames[k] frames, in either
         layout (utterance CMVN): one clx_norm_windows call behind the spec's own steps, a ranged spec's range step included; the
-        frames from valid_frames[k] on become the Norm's pad.  ValueError for a normalize that is not a Norm."""
+        frames from valid_frames[k] on become the Norm's pad.  ValueError for a normalize that is not a Norm.
+
+        With add=Add(...) the Add goes to that read() (starts counted at spec.sample_rate, every noise stream brought to one
+        channel): the features are those of the noisy waveform, for every spec -- a centred or reflected spec reflects the noisy
+        crop.  valid and valid_frames are the signal's."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
+        if add is not None and not isinstance(add, Add):
+            raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
         import torch
         if layout not in _LAYOUTS:
             raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
@@ -2072,7 +2213,7 @@ class StreamSet:
                 raise ValueError("read_mel: a centred spec needs length greater than n_fft // 2 = %d, not %d" % (P, L))
             if (n_frames - 1) * spec.hop + spec.n_fft > L + 2 * P:
                 raise ValueError("read_mel: length %d holds %d centred frames, not %d" % (L, 1 + (L + 2 * P - spec.n_fft) // spec.hop, n_frames))
-        audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1)
+        audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1, add=add)
         B = int(audio.shape[0])
         out = torch.empty((B, spec.n_out, n_frames) if layout == "ct" else (B, n_frames, spec.n_out), dtype=torch.float32,
                           device=audio.device)

@@ -14,6 +14,7 @@
 #include "clx_mix.hip"                  // (brings clx_resample.hip with it)
 #include "clx_mel.hip"
 #include "clx_norm.hip"
+#include "clx_add.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -279,6 +280,12 @@ struct clx_ctx {
     double* d_norm_part = nullptr; size_t norm_part_cap = 0;
     std::vector<void*> norm_old_dev, norm_old_host;
     hipEvent_t ev_norm_up = nullptr, ev_norm_done = nullptr; bool norm_used = false;
+    // clx_add_windows: the call's table (q, Vs, Vn, j per window; behind them on the device the gains) with its pinned staging and
+    // its two events, by the same rules, and the table of the call's double partial sums (device only)
+    void* d_add = nullptr; void* h_add = nullptr; size_t add_cap = 0;
+    double* d_add_part = nullptr; size_t add_part_cap = 0;
+    std::vector<void*> add_old_dev, add_old_host;
+    hipEvent_t ev_add_up = nullptr, ev_add_done = nullptr; bool add_used = false;
 };
 
 struct clx_mel_spec {
@@ -471,6 +478,12 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->norm_old_dev.push_back(ctx->d_norm); ctx->norm_old_dev.push_back(ctx->d_norm_part); ctx->norm_old_host.push_back(ctx->h_norm);
     for (void* p : ctx->norm_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->norm_old_host) if (p) (void)hipHostFree(p);
+    if (ctx->add_used) (void)hipEventSynchronize(ctx->ev_add_done);
+    if (ctx->ev_add_up) (void)hipEventDestroy(ctx->ev_add_up);
+    if (ctx->ev_add_done) (void)hipEventDestroy(ctx->ev_add_done);
+    ctx->add_old_dev.push_back(ctx->d_add); ctx->add_old_dev.push_back(ctx->d_add_part); ctx->add_old_host.push_back(ctx->h_add);
+    for (void* p : ctx->add_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->add_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1780,6 +1793,61 @@ extern "C" int clx_norm_windows(clx_ctx* ctx, void* d_data, size_t n_windows, ui
                        pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_norm_done, stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                               const void* d_noise, size_t n_noise, const uint32_t* noise_valid, const int32_t* noise_index,
+                               const float* snr_db, uint32_t layout, const clx_add_opts* opts, void* d_gains, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_add_plan pl;
+    const char* why = clx_add_check(d_data, n_windows, rows, T, valid, d_noise, n_noise, noise_valid, noise_index, snr_db, layout, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_chunks == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_add_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_add_up, hipEventDisableTiming));
+    if (!ctx->ev_add_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_add_done, hipEventDisableTiming));
+    const bool grow_tab = n_windows > ctx->add_cap, grow_part = pl.partials > ctx->add_part_cap;
+    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
+        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
+        double* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc add partial sums")) return CLX_API_ERROR;
+        if (ctx->d_add_part) ctx->add_old_dev.push_back(ctx->d_add_part);
+        ctx->d_add_part = d; ctx->add_part_cap = want;
+    }
+    if (grow_tab) {
+        const size_t want = n_windows + n_windows / 2 + 64;
+        void* d = nullptr; void* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&d, want * clx_add::kTableBytesDevice), "hipMalloc add table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc(&h, want * clx_add::kTableBytes, hipHostMallocDefault), "hipHostMalloc add table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_add) { ctx->add_old_dev.push_back(ctx->d_add); ctx->add_old_host.push_back(ctx->h_add); }
+        ctx->d_add = d; ctx->h_add = h; ctx->add_cap = want;
+    }
+    if (ctx->add_used) {
+        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_add_up));    // (the upload only: the earlier launch itself is not waited for)
+        if (!grow_tab || !grow_part) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_add_done, 0));
+    }
+    clx_add_fill(ctx->h_add, n_windows, valid, noise_valid, noise_index, snr_db);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_add, ctx->h_add, n_windows * clx_add::kTableBytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_add_up, stream));
+    ctx->add_used = true;                                      // (from here on the staging and the tables are in use)
+    float* const gain = (float*)((char*)ctx->d_add + n_windows * clx_add::kTableBytes);     // (behind this call's table)
+    const float* x = (const float*)d_data;
+    if (pl.tc)
+        hipLaunchKernelGGL(clx_k_add_sum_tc, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_noise,
+                           (const void*)ctx->d_add, ctx->d_add_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+    else
+        hipLaunchKernelGGL(clx_k_add_sum, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_noise,
+                           (const void*)ctx->d_add, ctx->d_add_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_add_gain, dim3(pl.gain_blocks), dim3(clx_add::kThreads), 0, stream, (const void*)ctx->d_add,
+                       (const double*)ctx->d_add_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_add_apply, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_add::kThreads), 0, stream, (float*)d_data,
+                       (const float*)d_noise, (const void*)ctx->d_add, (const float*)gain, (uint32_t)n_windows, rows, T, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_add_done, stream));
     return CLX_OK;
 }
 

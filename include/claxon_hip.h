@@ -669,6 +669,50 @@ int  clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const void* d_audio
 typedef struct { uint32_t mean, var, ddof; float eps, pad; } clx_norm_opts;
 int  clx_norm_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid, uint32_t layout,
                       const clx_norm_opts* opts, void* d_stats, void* stream);
+/* A second batch of windows added to a dense float32 batch at a target signal-to-noise ratio, in place on the device: noise or
+ * music behind speech, a second speaker, babble.  d_data is [n_windows][rows][T] (CLX_WINDOW_CT) or [n_windows][T][rows]
+ * (CLX_WINDOW_TC), rows in 1..8, and is modified; d_noise is [n_noise][rows][T] in the same layout and is never written.
+ * noise_index[k] = j names the noise window added to signal window k, -1 none; several k may name one j.  For window k, with
+ * x[r][t] its cells and n[r][t] those of noise window j:
+ *
+ *   Vs, Vn     Vs = valid[k]; Vn = min(noise_valid[j], Vs): the noise samples that fall inside the signal's live part.
+ *   Es         the sum over the rows r ascending, from +0.0, of the row sum of (double)x[r][t] * (double)x[r][t] over t < Vs (the
+ *              product is exact in double); each row sum in clx_norm_windows' ORDER with n = Vs: chunks of 4096, 64 strands, the xor
+ *              fold, the chunks' partials ascending from +0.0; every addition a double addition rounded once.
+ *   En         the same over n[r][t], t < Vn (ORDER with n = Vn).  The ORDER is a function of (t, count) alone, so CT and TC of the
+ *              same data give the same Es, En, g and cells bit for bit.
+ *   q          pow(10.0, -(double)snr_db[k] / 10.0), computed by the host's libm in double and handed to the device as a double in
+ *              the per-call table; q = 0 for snr_db[k] = +inf.  Nothing transcendental runs on the device.
+ *   g          (float)sqrt((Es * (double)Vn * q) / (En * (double)Vs)): double multiplications left to right in each bracket, one
+ *              double division, one correctly rounded double square root, one rounding to float32.  This is the ratio of MEAN
+ *              powers, each signal counted over its own live samples: 10 log10((Es / Vs) / (g^2 En / Vn)) = snr_db.  Where the
+ *              noise covers the window (Vn == Vs) it is the gain of torchaudio.functional.add_noise.
+ *              g = +0.0 where noise_index[k] < 0, Vs == 0, Vn == 0, Es == 0, En == 0 or q == 0.
+ *   range      nothing is clamped.  The double arithmetic cannot overflow on finite cells (a square is below 2^256, q below 2^67),
+ *              but the rounding to float32 can: a ratio beyond FLT_MAX (a loud signal over a noise of a few subnormal cells at
+ *              snr_db near -200) gives g = +inf, one far below the subnormals g = +0.0 (the window is then not rewritten).  With
+ *              g = +inf the cells are what IEEE gives: +-inf where n is not zero, NaN where it is.  Cells that are inf or NaN
+ *              themselves make Es or En inf or NaN, and g and the window's cells follow by the same rules; other windows do not.
+ *   cell       for t < Vn: fmaf(g, n[r][t], x[r][t]), one rounding.  Cells with Vn <= t < Vs and cells with t >= Vs (padding) keep
+ *              their words, whatever the noise holds there; a window with g == +0.0 is not rewritten at all; no noise cell with
+ *              t >= Vn is read, no data cell with t >= Vs.
+ *   gains      d_gains (may be NULL) is [n_windows] float32 and receives g of every window of a call that launches.
+ *
+ * opts is NULL or all zero (room for later).  valid, noise_valid, noise_index and snr_db are host arrays, staged as
+ * clx_norm_windows stages valid -- one pinned table a call (q, Vs, Vn, j per window), tables that have to grow replaced before
+ * anything is queued, one event behind the upload and one behind the last launch -- so the call is asynchronous on `stream`
+ * (NULL: the context's), returns without waiting for the device and the arrays may be reused at once.  The partial sums wait
+ * between the launches in a table of n_windows * 2 * rows * ceil(T / 4096) doubles that the context keeps, g in one of n_windows
+ * floats.  No floating-point atomics.  CLX_API_ERROR, each with a clx_last_error text of its own, for opts that are not zero, an
+ * unknown layout, rows outside 1..8, a null valid, noise_index or snr_db, a valid[k] > T, a noise_index[k] outside -1 ..
+ * n_noise - 1, a snr_db[k] that is NaN, one that is -inf or beyond 200 in magnitude, and -- where some noise_index[k] >= 0 -- a
+ * null d_data, d_noise or noise_valid and a noise_valid[j] > T.  n_windows == 0, T == 0 or every noise_index[k] == -1 succeeds,
+ * launches nothing and leaves d_gains alone.  Not here: tiling a short noise over a long window, several noises in one call,
+ * other gain rules (peak, loudness). */
+typedef struct { uint32_t reserved; } clx_add_opts;
+int  clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                     const void* d_noise, size_t n_noise, const uint32_t* noise_valid, const int32_t* noise_index,
+                     const float* snr_db, uint32_t layout, const clx_add_opts* opts, void* d_gains, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
