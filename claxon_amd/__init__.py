@@ -102,13 +102,13 @@ EXPORTS = [
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
-    "clx_norm_windows", "clx_add_windows",
+    "clx_norm_windows", "clx_add_windows", "clx_reverb_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -197,6 +197,7 @@ def lib():
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_norm_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.clx_add_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.clx_reverb_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -833,6 +834,60 @@ class Context:
         self._check(lib().clx_add_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), n_ptr, N, _np_ptr(noise_valid), _np_ptr(noise_index),
                                           _np_ptr(snr), int(layout), None, g_ptr, C.c_void_p(handle) if handle else None))
         return data
+
+    def reverb_windows(self, data, valid, ir, ir_len, ir_index, layout, out=None, keep_power=True, gains=None, stream=None):
+        """clx_reverb_windows: the dense float32 batch `data` -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows 1..8 --
+        convolved with the mono impulse responses `ir` ([N, K] float32, row j live for ir_len[j] taps), out of place: window k gets
+        response ir_index[k] (-1: none, a copy) on every row, as the ascending chain of fused multiply-adds that claxon_hip.h
+        defines; the window is the crop, cells from valid[k] on become zero.  keep_power=True then rescales every window to the power
+        of its dry signal (lhotse's normalize_output).  `out` has data's shape and must not overlap it (None: a new tensor);
+        `gains`, if given, is a [B] float32 tensor that receives every window's scale, 1 where nothing was scaled.  `data`, `ir`,
+        `out` and `gains` are CUDA float32 tensors, or `data` is a (pointer, B, rows, T) tuple, `ir` a (pointer, N, K) triple and
+        `out` and `gains` pointers.  `data` and `ir` are not written.  Asynchronous on `stream` as gather_windows is.  Returns `out`."""
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("reverb_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+            if out is None:
+                import torch
+                out = torch.empty_like(data)
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        if hasattr(out, "data_ptr"):
+            if not hasattr(data, "data_ptr") or tuple(out.shape) != tuple(data.shape) or not out.is_contiguous() or str(out.dtype) != "torch.float32":
+                raise ValueError("reverb_windows: out must be a contiguous float32 tensor of data's shape")
+        if hasattr(ir, "data_ptr"):
+            if ir.dim() != 2 or not ir.is_contiguous() or str(ir.dtype) != "torch.float32":
+                raise ValueError("reverb_windows: ir must be a contiguous float32 [N, K] tensor")
+            i_ptr, N, K = ir.data_ptr(), int(ir.shape[0]), int(ir.shape[1])
+        elif ir is None:
+            i_ptr, N, K = None, 0, 1
+        else:
+            i_ptr, N, K = (int(ir[0]) if ir[0] else None), int(ir[1]), int(ir[2])
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        ir_len = np.ascontiguousarray(ir_len if ir_len is not None else [], dtype=np.uint32).reshape(-1)
+        ir_index = np.ascontiguousarray(ir_index, dtype=np.int32).reshape(-1)
+        for name, a, want in (("valid", valid, B), ("ir_index", ir_index, B), ("ir_len", ir_len, N)):
+            if a.size != want:
+                raise ValueError("reverb_windows: %s has %d entries for %d windows" % (name, a.size, want))
+        for name, v in (("rows", rows), ("T", T), ("K", K), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("reverb_windows: %s is out of range" % name)
+        if hasattr(gains, "data_ptr"):
+            if tuple(gains.shape) != (B,) or not gains.is_contiguous() or str(gains.dtype) != "torch.float32":
+                raise ValueError("reverb_windows: gains must be a contiguous float32 [B] tensor")
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
+        g_ptr = gains.data_ptr() if hasattr(gains, "data_ptr") else (int(gains) if gains else None)
+        opts = _ReverbOpts(1 if keep_power else 0, 0)
+        self._check(lib().clx_reverb_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), i_ptr, N, K, _np_ptr(ir_len), _np_ptr(ir_index),
+                                             int(layout), C.byref(opts), o_ptr, g_ptr, C.c_void_p(handle) if handle else None))
+        return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
         a = _u8(arena)
@@ -1919,6 +1974,88 @@ class Add:
         return src, sel
 
 
+# ---- room impulse responses over the windows ------------------------------------------------------------------------------------
+
+REVERB_TAPS_LIMIT = 1 << 16            # the most taps of a response: clx_reverb_windows' K
+
+
+class _ReverbOpts(C.Structure):          # clx_reverb_opts
+    _fields_ = [("keep_power", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Reverb:
+    """What read(..., reverb=) and read_mel(..., reverb=) convolve their windows with (clx_reverb_windows, claxon_hip.h): window k
+    is convolved with stream stream_ids[k] of `source`, a StreamSet of the reading set's context that holds mono impulse responses;
+    a stream id of -1 leaves that window as it is.  The response is read from sample starts[k] on (a scalar or one value per
+    window, counted as read() counts them, at the call's sample rate: a caller skips the pre-delay with it) and truncated to `taps`
+    samples; taps=None takes the longest named response at that rate.  keep_power=True rescales every reverberated window to the
+    power of its dry signal.  The window is the crop: what the stream held before it leaves no tail in it.  A plain value: it owns
+    nothing on the device.  ValueError for a source that is no StreamSet, arrays that differ in length, an id below -1, a negative
+    start and taps outside 1 .. 65536; the read refuses lengths that differ from its own, an id the source does not have, a
+    response stream that is not mono, a closed source and a source of another context."""
+
+    def __init__(self, stream_ids, source, starts=0, taps=None, keep_power=True):
+        if not isinstance(source, StreamSet):
+            raise ValueError("Reverb: source must be a StreamSet, not %r" % (source,))
+        self.stream_ids = np.array(stream_ids, dtype=np.int64).reshape(-1)
+        st = np.array(starts, dtype=np.int64)
+        if st.ndim == 0:
+            st = np.full(self.stream_ids.size, st, dtype=np.int64)
+        self.starts = st.reshape(-1)
+        if self.stream_ids.size != self.starts.size:
+            raise ValueError("Reverb: starts must be a scalar or one value per window")
+        if self.stream_ids.size and self.stream_ids.min() < -1:
+            raise ValueError("Reverb: a stream id is below -1")
+        if np.any((self.starts < 0) & (self.stream_ids >= 0)):
+            raise ValueError("Reverb: a response starts before its stream")
+        if taps is not None:
+            if isinstance(taps, bool) or int(taps) != taps or not 1 <= int(taps) <= REVERB_TAPS_LIMIT:
+                raise ValueError("Reverb: taps must be None or a whole number in 1 .. %d, not %r" % (REVERB_TAPS_LIMIT, taps))
+            taps = int(taps)
+        self.taps = taps
+        self.keep_power = bool(keep_power)
+        self.source = source
+
+    def __len__(self):
+        return int(self.stream_ids.size)
+
+    def __repr__(self):
+        return "Reverb(%d windows, %d with a response, taps=%s, keep_power=%s)" % (len(self), int((self.stream_ids >= 0).sum()), self.taps,
+                                                                                   self.keep_power)
+
+    def _plan(self, reader, B, sample_rate, who):
+        """The refusals of a read of B windows at sample_rate (None: the streams' own): (the windows with a response, taps)."""
+        src = self.source
+        if src._descs is None:
+            raise ValueError("%s: reverb's source is closed" % who)
+        if src.ctx is not reader.ctx:
+            raise ValueError("%s: reverb's source belongs to another context" % who)
+        if len(self) != B:
+            raise ValueError("%s: reverb has %d windows, the call %d" % (who, len(self), B))
+        sel = np.nonzero(self.stream_ids >= 0)[0]
+        if sel.size and self.stream_ids.max() >= len(src):
+            raise ValueError("%s: reverb names a stream its source does not have" % who)
+        for k in sel.tolist():
+            s = int(self.stream_ids[k])
+            if src.problems[s] is None and src.channels[s] != 1:
+                raise ValueError("%s: response stream %d has %d channels, not one (window %d)" % (who, s, src.channels[s], k))
+        taps = self.taps
+        if taps is None and sel.size:                        # the longest named response, from its start on, at the call's rate
+            ids = self.stream_ids[sel]
+            named = [int(s) for s in ids.tolist() if src.problems[int(s)] is None]
+            if sample_rate is None:
+                lens = src._lengths[ids]
+            else:
+                _, pairs = src._check_rate(sample_rate, set(named), who)
+                lens = np.array([0 if src.problems[int(s)] is not None else
+                                 (int(src._lengths[int(s)]) * pairs[src.sample_rates[int(s)]][1] + pairs[src.sample_rates[int(s)]][0] - 1)
+                                 // pairs[src.sample_rates[int(s)]][0] for s in ids.tolist()], dtype=np.int64)
+            taps = int(np.clip(lens - self.starts[sel], 0, None).max())
+            if taps > REVERB_TAPS_LIMIT:
+                raise ValueError("%s: the longest response has %d samples, more than %d; taps= truncates it" % (who, taps, REVERB_TAPS_LIMIT))
+        return sel, int(taps or 0)
+
+
 # ---- sample windows from resident streams -----------------------------------------------------------------------------------------
 
 _LAYOUTS = {"tc": WINDOW_TC, "ct": WINDOW_CT}
@@ -2011,7 +2148,8 @@ class StreamSet:
                 out[s] = (int(self._lengths[s]) * n + o - 1) // o
         return torch.from_numpy(out)
 
-    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None, normalize=None, add=None, return_gains=False):
+    def read(self, stream_ids, starts, length, layout="tc", sample_rate=None, channels=None, normalize=None, add=None, return_gains=False,
+             reverb=None):
         """A batch of windows: window k is samples [starts[k], starts[k] + length) of stream stream_ids[k], positions counted as load()
         counts them (by cumulative block size in frame order; the frame headers' sample numbers are not consulted).  Returns (float32
         tensor on the context's GPU, contiguous: [B, length, C] for layout "tc", [B, C, length] for "ct"; valid): valid[k] =
@@ -2052,11 +2190,23 @@ class StreamSet:
         windows' channel count.  return_gains=True appends the windows' gains (float32 [B] on the GPU, 0 where nothing was added) to
         the return value.  ValueError for an add that is not an Add, whose length is not this call's, that names a stream its
         source does not have, or whose source is closed or of another context.  Tiling a short noise over a long window, several
-        Adds in one call and other gain rules are not offered."""
+        Adds in one call and other gain rules are not offered.
+
+        With reverb=Reverb(...) every window is convolved with a room impulse response between the crop (resampling and channels=
+        included) and add=, so that noise is added to the reverberant signal and normalize= sees both: one
+        source.read(ids, starts, taps, "ct", sample_rate=sample_rate, channels=None) on the Reverb's source for the windows whose
+        response id is not -1 -- the source's frames_decoded counts its frames --, then one clx_reverb_windows call behind both
+        (claxon_hip.h has the cells: an ascending chain of fused multiply-adds over the window, which is the crop; with keep_power
+        the window is then rescaled to its dry power).  Every channel of a window gets the same response.  valid is unchanged: the
+        tail past the window's end is cut.  return_gains keeps its meaning for add.  ValueError for a reverb that is not a Reverb,
+        whose length is not this call's, that names a stream its source does not have or one that is not mono, or whose source is
+        closed or of another context.  reverb=None is the call without the argument."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read: normalize must be a Norm or None, not %r" % (normalize,))
         if add is not None and not isinstance(add, Add):
             raise ValueError("read: add must be an Add or None, not %r" % (add,))
+        if reverb is not None and not isinstance(reverb, Reverb):
+            raise ValueError("read: reverb must be a Reverb or None, not %r" % (reverb,))
         import torch
         if self._descs is None:
             raise ValueError("read: the stream set is closed")
@@ -2094,6 +2244,8 @@ class StreamSet:
         mixed = bool(np.any(cw != ch))                       # (only with channels=K: some window is reduced or replicated)
         if add is not None:
             add_src, add_sel = add._plan(self, sid.size, ch, channels, "read")
+        if reverb is not None:
+            rv_sel, rv_taps = reverb._plan(self, sid.size, sample_rate, "read")
         B, dev = sid.size, "cuda:%d" % self.ctx.device
         if sample_rate is None:
             valid = np.clip(self._lengths[sid] - st, 0, length)
@@ -2150,6 +2302,13 @@ class StreamSet:
             else:
                 self.ctx.resample_windows(scratch, src_first, src_t0, src_n, np.where(valid > 0, st, 0), valid, rates, R, length, ch,
                                           _LAYOUTS[layout], out)
+        if reverb is not None and ch > 0 and rv_sel.size > 0 and rv_taps > 0:
+            ir, ir_len = reverb.source.read(reverb.stream_ids[rv_sel], reverb.starts[rv_sel], rv_taps, "ct", sample_rate=sample_rate, channels=None)
+            index = np.full(B, -1, dtype=np.int32)
+            index[rv_sel] = np.arange(rv_sel.size, dtype=np.int32)
+            # (out of place; the dry batch stays alive beside `ir` until the call returns, as the noise of add= does)
+            dry, out = out, self.ctx.reverb_windows(out, valid, ir.view(rv_sel.size, rv_taps), ir_len.numpy(), index, _LAYOUTS[layout],
+                                                    keep_power=reverb.keep_power)
         mixing = add is not None and ch > 0 and add_sel.size > 0
         # the gains: clx_add_windows writes every one of them when it runs, so they need no fill then -- a fill would run on torch's
         # stream, unordered against the context's own stream that the launches go to when torch's current stream is the default one
@@ -2164,7 +2323,7 @@ class StreamSet:
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -2187,11 +2346,16 @@ class StreamSet:
 
         With add=Add(...) the Add goes to that read() (starts counted at spec.sample_rate, every noise stream brought to one
         channel): the features are those of the noisy waveform, for every spec -- a centred or reflected spec reflects the noisy
-        crop.  valid and valid_frames are the signal's."""
+        crop.  valid and valid_frames are the signal's.
+
+        With reverb=Reverb(...) the Reverb goes to that read() too (starts and taps counted at spec.sample_rate), in front of the
+        Add: the features are those of the reverberant, then noisy, waveform."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
         if add is not None and not isinstance(add, Add):
             raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
+        if reverb is not None and not isinstance(reverb, Reverb):
+            raise ValueError("read_mel: reverb must be a Reverb or None, not %r" % (reverb,))
         import torch
         if layout not in _LAYOUTS:
             raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
@@ -2213,7 +2377,7 @@ class StreamSet:
                 raise ValueError("read_mel: a centred spec needs length greater than n_fft // 2 = %d, not %d" % (P, L))
             if (n_frames - 1) * spec.hop + spec.n_fft > L + 2 * P:
                 raise ValueError("read_mel: length %d holds %d centred frames, not %d" % (L, 1 + (L + 2 * P - spec.n_fft) // spec.hop, n_frames))
-        audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1, add=add)
+        audio, valid = self.read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1, add=add, reverb=reverb)
         B = int(audio.shape[0])
         out = torch.empty((B, spec.n_out, n_frames) if layout == "ct" else (B, n_frames, spec.n_out), dtype=torch.float32,
                           device=audio.device)

@@ -15,6 +15,7 @@
 #include "clx_mel.hip"
 #include "clx_norm.hip"
 #include "clx_add.hip"
+#include "clx_reverb.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -286,6 +287,12 @@ struct clx_ctx {
     double* d_add_part = nullptr; size_t add_part_cap = 0;
     std::vector<void*> add_old_dev, add_old_host;
     hipEvent_t ev_add_up = nullptr, ev_add_done = nullptr; bool add_used = false;
+    // clx_reverb_windows: the call's table (clx_add's four arrays, then len and idx per window; behind them on the device the gains)
+    // with its pinned staging and its two events, by the same rules, and the table of the call's double partial sums (device only)
+    void* d_rv = nullptr; void* h_rv = nullptr; size_t rv_cap = 0;
+    double* d_rv_part = nullptr; size_t rv_part_cap = 0;
+    std::vector<void*> rv_old_dev, rv_old_host;
+    hipEvent_t ev_rv_up = nullptr, ev_rv_done = nullptr; bool rv_used = false;
 };
 
 struct clx_mel_spec {
@@ -484,6 +491,12 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->add_old_dev.push_back(ctx->d_add); ctx->add_old_dev.push_back(ctx->d_add_part); ctx->add_old_host.push_back(ctx->h_add);
     for (void* p : ctx->add_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->add_old_host) if (p) (void)hipHostFree(p);
+    if (ctx->rv_used) (void)hipEventSynchronize(ctx->ev_rv_done);
+    if (ctx->ev_rv_up) (void)hipEventDestroy(ctx->ev_rv_up);
+    if (ctx->ev_rv_done) (void)hipEventDestroy(ctx->ev_rv_done);
+    ctx->rv_old_dev.push_back(ctx->d_rv); ctx->rv_old_dev.push_back(ctx->d_rv_part); ctx->rv_old_host.push_back(ctx->h_rv);
+    for (void* p : ctx->rv_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->rv_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1848,6 +1861,71 @@ extern "C" int clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uin
                        (const float*)d_noise, (const void*)ctx->d_add, (const float*)gain, (uint32_t)n_windows, rows, T, pl.tc, pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_add_done, stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_reverb_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                  const void* d_ir, size_t n_ir, uint32_t K, const uint32_t* ir_len, const int32_t* ir_index,
+                                  uint32_t layout, const clx_reverb_opts* opts, void* d_out, void* d_gains, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_reverb_plan pl;
+    const char* why = clx_reverb_check(d_data, n_windows, rows, T, valid, d_ir, n_ir, K, ir_len, ir_index, layout, opts, d_out, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_rv_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rv_up, hipEventDisableTiming));
+    if (!ctx->ev_rv_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rv_done, hipEventDisableTiming));
+    const bool grow_tab = n_windows > ctx->rv_cap, grow_part = pl.partials > ctx->rv_part_cap;
+    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
+        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
+        double* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc reverb partial sums")) return CLX_API_ERROR;
+        if (ctx->d_rv_part) ctx->rv_old_dev.push_back(ctx->d_rv_part);
+        ctx->d_rv_part = d; ctx->rv_part_cap = want;
+    }
+    if (grow_tab) {
+        const size_t want = n_windows + n_windows / 2 + 64;
+        void* d = nullptr; void* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&d, want * clx_reverb::kTableBytesDevice), "hipMalloc reverb table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc(&h, want * clx_reverb::kTableBytes, hipHostMallocDefault), "hipHostMalloc reverb table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_rv) { ctx->rv_old_dev.push_back(ctx->d_rv); ctx->rv_old_host.push_back(ctx->h_rv); }
+        ctx->d_rv = d; ctx->h_rv = h; ctx->rv_cap = want;
+    }
+    if (ctx->rv_used) {
+        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_rv_up));     // (the upload only: the earlier launch itself is not waited for)
+        if (!grow_tab || !grow_part) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_rv_done, 0));
+    }
+    clx_reverb_fill(ctx->h_rv, n_windows, valid, ir_len, ir_index, opts ? opts->keep_power : 0u);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rv, ctx->h_rv, n_windows * clx_reverb::kTableBytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_rv_up, stream));
+    ctx->rv_used = true;                                       // (from here on the staging and the tables are in use)
+    float* const gain = (float*)((char*)ctx->d_rv + n_windows * clx_reverb::kTableBytes);   // (behind this call's table)
+    const float* x = (const float*)d_data;
+    hipLaunchKernelGGL(clx_k_reverb, dim3((unsigned)(n_windows * rows * pl.n_tiles)), dim3(clx_reverb::kThreads), 0, stream, x, (const float*)d_ir,
+                       (const void*)ctx->d_rv, (float*)d_out, (uint32_t)n_windows, rows, T, K, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    if (pl.power) {                                            // clx_add's sums over (x, y): its table is the head of this one
+        if (pl.tc)
+            hipLaunchKernelGGL(clx_k_add_sum_tc, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
+                               (const void*)ctx->d_rv, ctx->d_rv_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+        else
+            hipLaunchKernelGGL(clx_k_add_sum, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
+                               (const void*)ctx->d_rv, ctx->d_rv_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (pl.power || d_gains) {
+        hipLaunchKernelGGL(clx_k_reverb_gain, dim3(pl.gain_blocks), dim3(clx_reverb::kThreads), 0, stream, (const void*)ctx->d_rv,
+                           (const double*)ctx->d_rv_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (pl.power) {
+        hipLaunchKernelGGL(clx_k_reverb_scale, dim3((unsigned)(n_windows * pl.lines * pl.scale_tiles)), dim3(clx_reverb::kThreads), 0, stream,
+                           (float*)d_out, (const void*)ctx->d_rv, (const float*)gain, (uint32_t)n_windows, pl.lines, pl.line_len, pl.mult,
+                           pl.scale_tiles);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_rv_done, stream));
     return CLX_OK;
 }
 

@@ -713,6 +713,54 @@ typedef struct { uint32_t reserved; } clx_add_opts;
 int  clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
                      const void* d_noise, size_t n_noise, const uint32_t* noise_valid, const int32_t* noise_index,
                      const float* snr_db, uint32_t layout, const clx_add_opts* opts, void* d_gains, void* stream);
+/* A dense float32 batch of windows convolved with room impulse responses, out of place on the device: reverberation, the step
+ * between the crop and clx_add_windows (noise is added to the reverberant speech).  d_data is [n_windows][rows][T] (CLX_WINDOW_CT)
+ * or [n_windows][T][rows] (CLX_WINDOW_TC), rows in 1..8, and is never written; d_out has the same shape and layout, must not
+ * overlap d_data, and receives every cell.  d_ir is [n_ir][K] float32, mono responses, row j live for its first ir_len[j] <= K
+ * taps, and is never written.  ir_index[k] = j names the response of window k, -1 none; several k may name one j.  For window k
+ * with V = valid[k], x[r][t] its cells, h[] row j of d_ir and L = ir_len[j]:
+ *
+ *   window     the window is the crop: the signal starts at its sample 0, and what the stream held before it is not part of it.
+ *   y[r][t]    for t < V: acc = +0.0f; for k = 0, 1, .., min(t, L - 1) in ascending order acc = fmaf(h[k], x[r][t - k], acc), each
+ *              step one rounding; y[r][t] = acc.  Every row is convolved with the same response.
+ *   before     a tap that reaches before the crop (k > t) is SKIPPED: it is not an fmaf(h[k], +0.0f, acc).  So an infinite or NaN
+ *              tap h[k] leaves the outputs t < k alone (it reaches y[r][t] for t >= k, as IEEE gives: inf * 0 = NaN), and an
+ *              accumulator of -0.0 stays -0.0.  A cell y[r][t] is a function of x[r][0 .. t] and h[0 .. min(t, L - 1)] alone.
+ *   not read   no tap h[k] with k >= L, and no tap with k >= V; no data cell with t >= V: whatever lies there -- NaNs, another
+ *              caller's words -- reaches nothing.
+ *   other      a cell with t >= V becomes +0.0f, in every window.  A window with ir_index[k] < 0 or L == 0 receives its own
+ *              words for t < V (a copy: -0.0 and NaN payloads survive).
+ *   layouts    CT and TC of the same data give the same words: a cell's chain does not know the layout.
+ *
+ * opts->keep_power = 1 (lhotse's normalize_output) rescales a window so that the reverberant signal has the dry signal's power:
+ *
+ *   Ex, Ey     the sums over the rows r ascending, from +0.0, of the row sums of (double)x[r][t]^2 and of (double)y[r][t]^2 over
+ *              t < V (the squares are exact in double), each row sum in clx_norm_windows' ORDER with n = V, exactly as
+ *              clx_add_windows defines Es: chunks of 4096, 64 strands, the xor fold, the chunks' partials ascending from +0.0.
+ *   g          (float)sqrt(Ex / Ey): one double division, one correctly rounded double square root, one rounding to float32.
+ *              g = 1 where the window has no response (ir_index[k] < 0, L == 0), V == 0, Ex == 0 or Ey == 0, and with
+ *              keep_power = 0.
+ *   cell       fl32(y[r][t] * g) for t < V, one float32 multiplication rounded once; a window with g == 1 is not rewritten.
+ *   range      nothing is clamped.  A ratio beyond float32 gives g = +inf or +0.0 and the cells are what IEEE gives (+-inf, NaN
+ *              for a zero cell; zeros).  A cell or tap that is inf or NaN makes Ex or Ey inf or NaN; g is then what the double
+ *              arithmetic gives (inf / inf = NaN, finite / inf = 0) and the window's cells follow; other windows do not.
+ *   gains      d_gains (may be NULL) is [n_windows] float32 and receives g of every window, 1 where nothing was scaled.
+ *
+ * opts is NULL (keep_power 0) or has keep_power 0 or 1 and reserved 0.  K is 1..65536 (4 s at 16 kHz): a condition of the
+ * interface, the cost of the direct form grows with the taps.  valid, ir_len and ir_index are host arrays, staged as
+ * clx_add_windows stages its arrays -- one pinned table a call, tables that have to grow replaced before anything is queued, one
+ * event behind the upload and one behind the last launch -- so the call is asynchronous on `stream` (NULL: the context's),
+ * returns without waiting for the device and the arrays may be reused at once.  The partial sums of keep_power wait between the
+ * launches in a table of n_windows * 2 * rows * ceil(T / 4096) doubles that the context keeps.  No floating-point atomics.
+ * CLX_API_ERROR, each with a clx_last_error text of its own, for opts with a keep_power above 1 or reserved bits, an unknown
+ * layout, rows outside 1..8, K outside 1..65536, a null d_data, d_out, valid or ir_index, a null d_ir or ir_len with n_ir > 0, an
+ * ir_len[j] > K, a valid[k] > T, an ir_index[k] outside -1 .. n_ir - 1 and a d_out that overlaps d_data.  n_windows == 0 or
+ * T == 0 succeeds and launches nothing.  Not here: an FFT or overlap-save form, multi-channel responses, the tail of what the
+ * stream held before the crop. */
+typedef struct { uint32_t keep_power, reserved; } clx_reverb_opts;
+int  clx_reverb_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                        const void* d_ir, size_t n_ir, uint32_t K, const uint32_t* ir_len, const int32_t* ir_index,
+                        uint32_t layout, const clx_reverb_opts* opts, void* d_out, void* d_gains, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
