@@ -102,13 +102,13 @@ EXPORTS = [
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
-    "clx_norm_windows", "clx_add_windows", "clx_reverb_windows",
+    "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -198,6 +198,7 @@ def lib():
     L.clx_norm_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.clx_add_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.clx_reverb_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
+    L.clx_reverb_windows_fft.argtypes = L.clx_reverb_windows.argtypes
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -835,7 +836,7 @@ class Context:
                                           _np_ptr(snr), int(layout), None, g_ptr, C.c_void_p(handle) if handle else None))
         return data
 
-    def reverb_windows(self, data, valid, ir, ir_len, ir_index, layout, out=None, keep_power=True, gains=None, stream=None):
+    def reverb_windows(self, data, valid, ir, ir_len, ir_index, layout, out=None, keep_power=True, gains=None, stream=None, method="direct"):
         """clx_reverb_windows: the dense float32 batch `data` -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows 1..8 --
         convolved with the mono impulse responses `ir` ([N, K] float32, row j live for ir_len[j] taps), out of place: window k gets
         response ir_index[k] (-1: none, a copy) on every row, as the ascending chain of fused multiply-adds that claxon_hip.h
@@ -843,7 +844,11 @@ class Context:
         of its dry signal (lhotse's normalize_output).  `out` has data's shape and must not overlap it (None: a new tensor);
         `gains`, if given, is a [B] float32 tensor that receives every window's scale, 1 where nothing was scaled.  `data`, `ir`,
         `out` and `gains` are CUDA float32 tensors, or `data` is a (pointer, B, rows, T) tuple, `ir` a (pointer, N, K) triple and
-        `out` and `gains` pointers.  `data` and `ir` are not written.  Asynchronous on `stream` as gather_windows is.  Returns `out`."""
+        `out` and `gains` pointers.  `data` and `ir` are not written.  Asynchronous on `stream` as gather_windows is.  Returns `out`.
+        method="fft" is clx_reverb_windows_fft: the same arguments, refusals and keep_power, the cells by uniformly partitioned
+        overlap-save as claxon_hip.h defines it -- close to the direct form's, not its words; method="auto" takes it from REVERB_FFT_TAPS
+        taps (K) on and the direct form below; ValueError for any other method."""
+        _reverb_method(method, "reverb_windows")
         tc = int(layout) == WINDOW_TC
         if hasattr(data, "data_ptr"):
             if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
@@ -884,9 +889,12 @@ class Context:
         handle = getattr(stream, "cuda_stream", stream)
         o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
         g_ptr = gains.data_ptr() if hasattr(gains, "data_ptr") else (int(gains) if gains else None)
-        opts = _ReverbOpts(1 if keep_power else 0, 0)
-        self._check(lib().clx_reverb_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), i_ptr, N, K, _np_ptr(ir_len), _np_ptr(ir_index),
-                                             int(layout), C.byref(opts), o_ptr, g_ptr, C.c_void_p(handle) if handle else None))
+        if reverb_method_for(method, K) == "fft":
+            opts, call = _ReverbFftOpts(1 if keep_power else 0), lib().clx_reverb_windows_fft
+        else:
+            opts, call = _ReverbOpts(1 if keep_power else 0, 0), lib().clx_reverb_windows
+        self._check(call(self._h, d_ptr, B, rows, T, _np_ptr(valid), i_ptr, N, K, _np_ptr(ir_len), _np_ptr(ir_index),
+                         int(layout), C.byref(opts), o_ptr, g_ptr, C.c_void_p(handle) if handle else None))
         return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -1983,18 +1991,44 @@ class _ReverbOpts(C.Structure):          # clx_reverb_opts
     _fields_ = [("keep_power", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _ReverbFftOpts(C.Structure):       # clx_reverb_fft_opts
+    _fields_ = [("keep_power", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+REVERB_METHODS = ("direct", "fft", "auto")      # clx_reverb_windows, clx_reverb_windows_fft, the choice between them by the taps
+# method="auto" takes the FFT form from this many taps on: the smallest probed tap count from which read(reverb=, method="fft") is
+# faster than the direct form's read by more than the run-to-run spread (profiles/reverb_fft_probe.txt: at 800 taps 3.64 ms against
+# 3.62 ms, no gain; at 4 000 taps 3.60 ms against 4.98 ms, the slowest FFT read faster than the fastest direct one)
+REVERB_FFT_TAPS = 4000
+
+
+def _reverb_method(method, who):
+    if not isinstance(method, str) or method not in REVERB_METHODS:
+        raise ValueError("%s: method must be one of %s, not %r" % (who, ", ".join(repr(m) for m in REVERB_METHODS), method))
+    return method
+
+
+def reverb_method_for(method, taps):
+    """The method a call with responses of `taps` taps (clx_reverb_windows' K) runs: "auto" is "fft" from REVERB_FFT_TAPS on."""
+    method = _reverb_method(method, "reverb_method_for")
+    return method if method != "auto" else ("fft" if int(taps) >= REVERB_FFT_TAPS else "direct")
+
+
 class Reverb:
     """What read(..., reverb=) and read_mel(..., reverb=) convolve their windows with (clx_reverb_windows, claxon_hip.h): window k
     is convolved with stream stream_ids[k] of `source`, a StreamSet of the reading set's context that holds mono impulse responses;
     a stream id of -1 leaves that window as it is.  The response is read from sample starts[k] on (a scalar or one value per
     window, counted as read() counts them, at the call's sample rate: a caller skips the pre-delay with it) and truncated to `taps`
     samples; taps=None takes the longest named response at that rate.  keep_power=True rescales every reverberated window to the
-    power of its dry signal.  The window is the crop: what the stream held before it leaves no tail in it.  A plain value: it owns
+    power of its dry signal.  method="direct" (the default) convolves with clx_reverb_windows, method="fft" with
+    clx_reverb_windows_fft, the partitioned FFT form for long responses, method="auto" with the latter from REVERB_FFT_TAPS taps on
+    (the taps of the call: `taps`, or the longest named response).  The window is the crop: what the stream held before it leaves no tail in it.  A plain value: it owns
     nothing on the device.  ValueError for a source that is no StreamSet, arrays that differ in length, an id below -1, a negative
-    start and taps outside 1 .. 65536; the read refuses lengths that differ from its own, an id the source does not have, a
+    start, taps outside 1 .. 65536 and a method that is neither; the read refuses lengths that differ from its own, an id the source does not have, a
     response stream that is not mono, a closed source and a source of another context."""
 
-    def __init__(self, stream_ids, source, starts=0, taps=None, keep_power=True):
+    def __init__(self, stream_ids, source, starts=0, taps=None, keep_power=True, method="direct"):
+        self.method = _reverb_method(method, "Reverb")
         if not isinstance(source, StreamSet):
             raise ValueError("Reverb: source must be a StreamSet, not %r" % (source,))
         self.stream_ids = np.array(stream_ids, dtype=np.int64).reshape(-1)
@@ -2020,8 +2054,8 @@ class Reverb:
         return int(self.stream_ids.size)
 
     def __repr__(self):
-        return "Reverb(%d windows, %d with a response, taps=%s, keep_power=%s)" % (len(self), int((self.stream_ids >= 0).sum()), self.taps,
-                                                                                   self.keep_power)
+        return "Reverb(%d windows, %d with a response, taps=%s, keep_power=%s, method=%r)" % (len(self), int((self.stream_ids >= 0).sum()), self.taps,
+                                                                                              self.keep_power, self.method)
 
     def _plan(self, reader, B, sample_rate, who):
         """The refusals of a read of B windows at sample_rate (None: the streams' own): (the windows with a response, taps)."""
@@ -2308,7 +2342,7 @@ class StreamSet:
             index[rv_sel] = np.arange(rv_sel.size, dtype=np.int32)
             # (out of place; the dry batch stays alive beside `ir` until the call returns, as the noise of add= does)
             dry, out = out, self.ctx.reverb_windows(out, valid, ir.view(rv_sel.size, rv_taps), ir_len.numpy(), index, _LAYOUTS[layout],
-                                                    keep_power=reverb.keep_power)
+                                                    keep_power=reverb.keep_power, method=reverb.method)
         mixing = add is not None and ch > 0 and add_sel.size > 0
         # the gains: clx_add_windows writes every one of them when it runs, so they need no fill then -- a fill would run on torch's
         # stream, unordered against the context's own stream that the launches go to when torch's current stream is the default one

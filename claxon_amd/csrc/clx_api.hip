@@ -16,6 +16,7 @@
 #include "clx_norm.hip"
 #include "clx_add.hip"
 #include "clx_reverb.hip"
+#include "clx_reverb_fft.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -293,6 +294,15 @@ struct clx_ctx {
     double* d_rv_part = nullptr; size_t rv_part_cap = 0;
     std::vector<void*> rv_old_dev, rv_old_host;
     hipEvent_t ev_rv_up = nullptr, ev_rv_done = nullptr; bool rv_used = false;
+    // clx_reverb_windows_fft: the same set of its own (the table's capacity counted in bytes: it ends in the call's partition jobs),
+    // the workspace of the segment and partition spectra, kept and grown the way the partial sums are, and the twiddles (written
+    // once, by the first call)
+    void* d_rvf = nullptr; void* h_rvf = nullptr; size_t rvf_cap = 0;
+    double* d_rvf_part = nullptr; size_t rvf_part_cap = 0;
+    void* d_rvf_ws = nullptr; size_t rvf_ws_cap = 0;
+    void* d_rvf_tw = nullptr;
+    std::vector<void*> rvf_old_dev, rvf_old_host;
+    hipEvent_t ev_rvf_up = nullptr, ev_rvf_done = nullptr; bool rvf_used = false;
 };
 
 struct clx_mel_spec {
@@ -497,6 +507,13 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->rv_old_dev.push_back(ctx->d_rv); ctx->rv_old_dev.push_back(ctx->d_rv_part); ctx->rv_old_host.push_back(ctx->h_rv);
     for (void* p : ctx->rv_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->rv_old_host) if (p) (void)hipHostFree(p);
+    if (ctx->rvf_used) (void)hipEventSynchronize(ctx->ev_rvf_done);
+    if (ctx->ev_rvf_up) (void)hipEventDestroy(ctx->ev_rvf_up);
+    if (ctx->ev_rvf_done) (void)hipEventDestroy(ctx->ev_rvf_done);
+    ctx->rvf_old_dev.push_back(ctx->d_rvf); ctx->rvf_old_dev.push_back(ctx->d_rvf_part); ctx->rvf_old_dev.push_back(ctx->d_rvf_ws);
+    ctx->rvf_old_dev.push_back(ctx->d_rvf_tw); ctx->rvf_old_host.push_back(ctx->h_rvf);
+    for (void* p : ctx->rvf_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->rvf_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1926,6 +1943,94 @@ extern "C" int clx_reverb_windows(clx_ctx* ctx, const void* d_data, size_t n_win
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_rv_done, stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_reverb_windows_fft(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                      const void* d_ir, size_t n_ir, uint32_t K, const uint32_t* ir_len, const int32_t* ir_index,
+                                      uint32_t layout, const clx_reverb_fft_opts* opts, void* d_out, void* d_gains, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_reverb_plan pl;
+    clx_rvfft_plan fp;
+    std::string why = clx_rvfft_check(d_data, n_windows, rows, T, valid, d_ir, n_ir, K, ir_len, ir_index, layout, opts, d_out, &pl);
+    if (!why.empty()) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    why = clx_rvfft_plan_call(n_windows, rows, T, valid, ir_len, ir_index, n_ir, &fp);
+    if (!why.empty()) { ctx->last_error = why; return CLX_API_ERROR; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_rvf_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rvf_up, hipEventDisableTiming));
+    if (!ctx->ev_rvf_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rvf_done, hipEventDisableTiming));
+    if (!ctx->d_rvf_tw) {                                      // the twiddles, once (the one copy that is waited for)
+        std::vector<clx_rvfft::cf> tw(clx_rvfft::kN / 2u);
+        clx_rvfft_twiddles(tw.data());
+        void* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&d, tw.size() * sizeof(clx_rvfft::cf)), "hipMalloc reverb twiddles")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipMemcpy(d, tw.data(), tw.size() * sizeof(clx_rvfft::cf), hipMemcpyHostToDevice), "hipMemcpy reverb twiddles")) { (void)hipFree(d); return CLX_API_ERROR; }
+        ctx->d_rvf_tw = d;
+    }
+    const size_t tab_bytes = fp.table_bytes(n_windows), ws_bytes = (size_t)fp.slots() * clx_rvfft::kSpec * sizeof(clx_rvfft::cf);
+    const bool grow_tab = tab_bytes > ctx->rvf_cap, grow_part = pl.partials > ctx->rvf_part_cap, grow_ws = ws_bytes > ctx->rvf_ws_cap;
+    if (grow_ws) {                                             // larger tables, before anything is queued; the old ones are not freed here
+        const size_t want = ws_bytes + ws_bytes / 2;
+        void* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&d, want), "hipMalloc reverb spectra (the workspace of clx_reverb_windows_fft)")) return CLX_API_ERROR;
+        if (ctx->d_rvf_ws) ctx->rvf_old_dev.push_back(ctx->d_rvf_ws);
+        ctx->d_rvf_ws = d; ctx->rvf_ws_cap = want;
+    }
+    if (grow_part) {
+        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
+        double* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc reverb partial sums")) return CLX_API_ERROR;
+        if (ctx->d_rvf_part) ctx->rvf_old_dev.push_back(ctx->d_rvf_part);
+        ctx->d_rvf_part = d; ctx->rvf_part_cap = want;
+    }
+    if (grow_tab) {
+        const size_t want = tab_bytes + tab_bytes / 2 + 4096;
+        void* d = nullptr; void* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&d, want), "hipMalloc reverb table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc(&h, want, hipHostMallocDefault), "hipHostMalloc reverb table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_rvf) { ctx->rvf_old_dev.push_back(ctx->d_rvf); ctx->rvf_old_host.push_back(ctx->h_rvf); }
+        ctx->d_rvf = d; ctx->h_rvf = h; ctx->rvf_cap = want;
+    }
+    if (ctx->rvf_used) {
+        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_rvf_up));    // (the upload only: the earlier launch itself is not waited for)
+        if (!grow_tab || !grow_part || !grow_ws) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_rvf_done, 0));
+    }
+    clx_rvfft_fill(ctx->h_rvf, n_windows, valid, ir_len, ir_index, opts ? opts->keep_power : 0u, &fp);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rvf, ctx->h_rvf, tab_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_rvf_up, stream));
+    ctx->rvf_used = true;                                      // (from here on the staging and the tables are in use)
+    float* const gain = (float*)((char*)ctx->d_rvf + n_windows * clx_reverb::kTableBytes);  // (behind clx_reverb's part of the table)
+    const float* x = (const float*)d_data;
+    const clx_rvfft::cf* tw = (const clx_rvfft::cf*)ctx->d_rvf_tw;
+    hipLaunchKernelGGL(clx_k_rvfft_fwd, dim3((unsigned)fp.slots()), dim3(clx_rvfft::kThreads), 0, stream, x, (const float*)d_ir, (const void*)ctx->d_rvf, tw,
+                       (clx_rvfft::cf*)ctx->d_rvf_ws, (uint32_t)n_windows, rows, T, K, pl.tc, fp.nb, (uint32_t)fp.n_seg);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_rvfft_mac, dim3((unsigned)fp.n_seg), dim3(clx_rvfft::kThreads), 0, stream, x, (const void*)ctx->d_rvf, tw,
+                       (const clx_rvfft::cf*)ctx->d_rvf_ws, (float*)d_out, (uint32_t)n_windows, rows, T, pl.tc, fp.nb, (uint32_t)fp.n_seg);
+    HIP_TRY(ctx, hipGetLastError());
+    if (pl.power) {                                            // clx_add's sums over (x, y): its table is the head of this one
+        if (pl.tc)
+            hipLaunchKernelGGL(clx_k_add_sum_tc, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
+                               (const void*)ctx->d_rvf, ctx->d_rvf_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+        else
+            hipLaunchKernelGGL(clx_k_add_sum, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
+                               (const void*)ctx->d_rvf, ctx->d_rvf_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (pl.power || d_gains) {
+        hipLaunchKernelGGL(clx_k_reverb_gain, dim3(pl.gain_blocks), dim3(clx_reverb::kThreads), 0, stream, (const void*)ctx->d_rvf,
+                           (const double*)ctx->d_rvf_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (pl.power) {
+        hipLaunchKernelGGL(clx_k_reverb_scale, dim3((unsigned)(n_windows * pl.lines * pl.scale_tiles)), dim3(clx_reverb::kThreads), 0, stream,
+                           (float*)d_out, (const void*)ctx->d_rvf, (const float*)gain, (uint32_t)n_windows, pl.lines, pl.line_len, pl.mult,
+                           pl.scale_tiles);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_rvf_done, stream));
     return CLX_OK;
 }
 

@@ -755,12 +755,62 @@ int  clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows
  * CLX_API_ERROR, each with a clx_last_error text of its own, for opts with a keep_power above 1 or reserved bits, an unknown
  * layout, rows outside 1..8, K outside 1..65536, a null d_data, d_out, valid or ir_index, a null d_ir or ir_len with n_ir > 0, an
  * ir_len[j] > K, a valid[k] > T, an ir_index[k] outside -1 .. n_ir - 1 and a d_out that overlaps d_data.  n_windows == 0 or
- * T == 0 succeeds and launches nothing.  Not here: an FFT or overlap-save form, multi-channel responses, the tail of what the
- * stream held before the crop. */
+ * T == 0 succeeds and launches nothing.  Not here: an FFT or overlap-save form (that is clx_reverb_windows_fft below, a second method
+ * with a definition of its own), multi-channel responses, the tail of what the stream held before the crop. */
 typedef struct { uint32_t keep_power, reserved; } clx_reverb_opts;
 int  clx_reverb_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
                         const void* d_ir, size_t n_ir, uint32_t K, const uint32_t* ir_len, const int32_t* ir_index,
                         uint32_t layout, const clx_reverb_opts* opts, void* d_out, void* d_gains, void* stream);
+/* The same convolution by uniformly partitioned overlap-save: a second method beside clx_reverb_windows for long responses, whose
+ * work does not grow with the taps the way the direct form's does.  The arguments, their shapes and the refusals are
+ * clx_reverb_windows' (each text under this call's name); opts is NULL (keep_power 0) or has keep_power 0 or 1 and reserved[] all 0.
+ * The call is out of place, asynchronous on `stream`, stages its host arrays as clx_reverb_windows does (a table of 40 bytes a
+ * window and 12 a transformed partition) and never writes d_data or d_ir.  Its cells are NOT the direct form's words: they are the
+ * words of the schedule below, within the bound of DESIGN.md 4.19 of the exact convolution.  With H = 1024, N = 2 H = 2048, for
+ * window k with V = valid[k], L = ir_len[j], Lv = min(L, V), x[r][t] its cells (+0.0f for t < 0 and for t >= V) and h[] its taps
+ * (+0.0f for k >= Lv):
+ *
+ *   twiddles   tw[q] = (fl32(cos(2 pi q / N)), fl32(-sin(2 pi q / N))), q = 0 .. N / 2 - 1: the host's double cos and sin of the
+ *              double 2 pi q / N, each rounded once to float32.  One table, uploaded once; no device sine or cosine.
+ *   transform  F(w), of N real words w[n]: a[rev(n)] = (w[n], +0.0f), rev the reversal of the 11 bits of n.  Then the stages
+ *              s = 1 .. 11 in this order, radix 2, decimation in time; stage s has half = 2^(s - 1), and its butterflies
+ *              i = 0 .. N / 2 - 1 (independent of each other) have k = i mod half, lo = 2 (i - k) + k, hi = lo + half,
+ *              w = tw[k * (N / 2) / half], u = a[lo], v = a[hi] and
+ *                t.re = fmaf(w.re, v.re, -fl(w.im * v.im))        t.im = fmaf(w.re, v.im, fl(w.im * v.re))
+ *                a[lo] = (fl(u.re + t.re), fl(u.im + t.im))       a[hi] = (fl(u.re - t.re), fl(u.im - t.im))
+ *              : two rounded multiplications, two fmaf and four rounded additions a butterfly.  Bins 0 .. N / 2 of a[] are kept.
+ *              The inverse stages G(a) are the same with w.im negated (exact).
+ *   segments   X[s] = F(x[r][(s - 1) H + n], n = 0 .. N - 1) for s = 0 .. ceil(V / H) - 1.
+ *   partitions Hp[p] = F(h[p H + n] for n < H, +0.0f for n >= H) for p = 0 .. P - 1, P = ceil(Lv / H).
+ *   block b    (the outputs t = b H .. b H + H - 1, b H < V) per kept bin, p ascending from the p = 0 product:
+ *                p = 0:  Y.re = fmaf(X.re, Hp.re, -fl(X.im * Hp.im))                Y.im = fmaf(X.re, Hp.im, fl(X.im * Hp.re))
+ *                p >= 1: Y.re = fmaf(-X.im, Hp.im, fmaf(X.re, Hp.re, Y.re))         Y.im = fmaf(X.im, Hp.re, fmaf(X.re, Hp.im, Y.im))
+ *              with X = X[b - p], Hp = Hp[p], over p = 0 .. min(b, P - 1).  Then a[rev(n)] = Y[n] for n <= N / 2 and the
+ *              conjugate (Y[N - n].re, -Y[N - n].im) for n > N / 2, the inverse stages, and
+ *              y[r][b H + n] = fl(a[H + n].re * 2^-11) for n < H, b H + n < V: the scaling by 1 / N, exact but for underflow.
+ *   locality   the words of y[r][t] are a function of x[r][0 .. V), h[0 .. Lv), V and L alone: not of the layout (CT and TC give
+ *              the same words), the row count, the other rows, the other windows or the batch.  No two rows or windows share a
+ *              transform.  A partition's spectrum is computed once for all windows that read the same taps of it.
+ *   not read   no data cell with t >= V, no tap with k >= Lv: what lies there reaches nothing.  A partition wholly behind every
+ *              naming window's Lv and a segment wholly behind V are not transformed.
+ *   other      a cell with t >= V becomes +0.0f; a window with ir_index[k] < 0 or L == 0 receives its own words for t < V.
+ *   non-finite the contract covers finite live cells and taps.  UNLIKE the direct form, which skips a tap before the crop and so
+ *              keeps a NaN or infinite tap h[k] from the outputs t < k, every output of a block depends on every tap and every
+ *              sample the block's transforms read: a window with a non-finite live cell or tap has unspecified cells for t < V
+ *              (and an unspecified gain).  Every other window's words are untouched.
+ *   keep_power exactly clx_reverb_windows': Ex, Ey by clx_add's sum kernels over (d_data, d_out), the same g, the same g = 1
+ *              cases, the same cell = fl32(y * g), the same d_gains.
+ *
+ * Workspace: the spectra wait between the two launches in a table the context keeps and grows, of
+ * (n_windows * rows * ceil(T / H) + Q) * 8320 bytes, Q the partitions transformed: per response the whole partitions some window
+ * reads (max over its windows of floor(Lv / H)) and one ragged partition for every distinct (response, Lv) with Lv mod H != 0.
+ * An allocation that fails is CLX_API_ERROR with "hipMalloc reverb spectra" in clx_last_error, before anything is queued.  The
+ * partial sums of keep_power are as in clx_reverb_windows.  No floating-point atomics.  K keeps the 1..65536 limit.  Not here:
+ * multi-channel responses, tails from audio before the crop, spectra cached across calls, non-uniform partitions. */
+typedef struct { uint32_t keep_power, reserved[3]; } clx_reverb_fft_opts;
+int  clx_reverb_windows_fft(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                            const void* d_ir, size_t n_ir, uint32_t K, const uint32_t* ir_len, const int32_t* ir_index,
+                            uint32_t layout, const clx_reverb_fft_opts* opts, void* d_out, void* d_gains, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
