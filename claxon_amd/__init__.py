@@ -102,13 +102,13 @@ EXPORTS = [
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
-    "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft",
+    "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -199,6 +199,7 @@ def lib():
     L.clx_add_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.clx_reverb_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_reverb_windows_fft.argtypes = L.clx_reverb_windows.argtypes
+    L.clx_specaug_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -895,6 +896,57 @@ class Context:
             opts, call = _ReverbOpts(1 if keep_power else 0, 0), lib().clx_reverb_windows
         self._check(call(self._h, d_ptr, B, rows, T, _np_ptr(valid), i_ptr, N, K, _np_ptr(ir_len), _np_ptr(ir_index),
                          int(layout), C.byref(opts), o_ptr, g_ptr, C.c_void_p(handle) if handle else None))
+        return out
+
+    def specaug_windows(self, data, valid, layout, warp=None, freq_masks=None, time_masks=None, fill="mean", out=None, fills=None, stream=None):
+        """clx_specaug_windows: SpecAugment of the dense float32 feature batch `data` -- [B, rows, T] (WINDOW_CT) or [B, T, rows]
+        (WINDOW_TC), rows 1..256 --, out of place: window k's first valid[k] frames are warped in time about the pair warp[k] =
+        (c, w) (output frames [0, w) are input frames [0, c) resized by the bicubic rule of claxon_hip.h, [w, valid[k]) are
+        [c, valid[k]); (0, 0): no warp), then the rows of freq_masks[k] ([F, 2]: first row, width) and the frames of
+        time_masks[k] ([M, 2]: first output frame, width; F, M <= 32) become the fill: a float, or "mean", the mean of the window's
+        live input cells.  Frames from valid[k] on are copied as they are.  warp is [B, 2], freq_masks [B, F, 2], time_masks
+        [B, M, 2], whole numbers that are not negative; each may be None.  `out` has data's shape and must not be data (None: a
+        new tensor); `fills`, if given, is a [B] float32 tensor that receives every window's fill.  `data`, `out` and `fills`
+        are CUDA float32 tensors, or `data` is a (pointer, B, rows, T) tuple and `out` and `fills` pointers.  `data` is not
+        written.  Asynchronous on `stream` as gather_windows is.  Returns `out`."""
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("specaug_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+            if out is None:
+                import torch
+                out = torch.empty_like(data)
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        if hasattr(out, "data_ptr"):
+            if not hasattr(data, "data_ptr") or tuple(out.shape) != tuple(data.shape) or not out.is_contiguous() or str(out.dtype) != "torch.float32":
+                raise ValueError("specaug_windows: out must be a contiguous float32 tensor of data's shape")
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("specaug_windows: valid has %d entries for %d windows" % (valid.size, B))
+        warp = _specaug_table(warp, B, "warp", pairs=False)
+        fm = _specaug_table(freq_masks, B, "freq_masks")
+        tm = _specaug_table(time_masks, B, "time_masks")
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("specaug_windows: %s is out of range" % name)
+        mean, value = _specaug_fill(fill, "specaug_windows")
+        if hasattr(fills, "data_ptr"):
+            if tuple(fills.shape) != (B,) or not fills.is_contiguous() or str(fills.dtype) != "torch.float32":
+                raise ValueError("specaug_windows: fills must be a contiguous float32 [B] tensor")
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
+        f_ptr = fills.data_ptr() if hasattr(fills, "data_ptr") else (int(fills) if fills else None)
+        opts = _SpecAugOpts(0 if fm is None else fm.shape[1], 0 if tm is None else tm.shape[1], 1 if mean else 0, value, 0)
+        self._check(lib().clx_specaug_windows(self._h, d_ptr, o_ptr, B, rows, T, _np_ptr(valid), int(layout),
+                                              None if warp is None else _np_ptr(warp), None if fm is None else _np_ptr(fm),
+                                              None if tm is None else _np_ptr(tm), C.byref(opts), f_ptr,
+                                              C.c_void_p(handle) if handle else None))
         return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -1921,6 +1973,165 @@ class Norm:
         return hash((self.mean, self.var, self.ddof, self.eps, self.pad))
 
 
+# ---- SpecAugment ----------------------------------------------------------------------------------------------------------------
+
+SPECAUG_MAX_MASKS = 32
+
+
+class _SpecAugOpts(C.Structure):         # clx_specaug_opts
+    _fields_ = [("n_freq_masks", C.c_uint32), ("n_time_masks", C.c_uint32), ("fill_mean", C.c_uint32), ("fill", C.c_float), ("reserved", C.c_uint32)]
+
+
+def _specaug_fill(fill, who):
+    """(the fill is the mean, the constant as a float32 value) of a fill argument: "mean" or a finite number."""
+    if isinstance(fill, str):
+        if fill != "mean":
+            raise ValueError("%s: fill must be 'mean' or a finite number, not %r" % (who, fill))
+        return True, 0.0
+    if isinstance(fill, bool) or not isinstance(fill, (int, float, np.integer, np.floating)) or not math.isfinite(float(fill)) \
+            or abs(float(fill)) > float(np.finfo(np.float32).max):
+        raise ValueError("%s: fill must be 'mean' or a finite number, not %r" % (who, fill))
+    return False, float(np.float32(fill))
+
+
+def _specaug_table(a, B, name, pairs=True):
+    """A warp ([B, 2]) or mask ([B, n, 2]) argument as a contiguous uint32 array, None for None or a table without entries."""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.size == 0:
+        return None
+    if a.dtype.kind not in "iu" or (a.dtype.kind == "i" and a.min() < 0) or int(a.max()) >= 1 << 32:
+        raise ValueError("specaug: %s must hold whole numbers from 0 up" % name)
+    if (a.ndim != 3 if pairs else a.ndim != 2) or a.shape[0] != B or a.shape[-1] != 2:
+        raise ValueError("specaug: %s must be [%d, %s2], not %r" % (name, B, "n, " if pairs else "", tuple(a.shape)))
+    if pairs and a.shape[1] > SPECAUG_MAX_MASKS:
+        raise ValueError("specaug: %s has %d masks a window, more than %d" % (name, a.shape[1], SPECAUG_MAX_MASKS))
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _specaug_fit(plan, valid_frames, rows, n_frames, who):
+    """ValueError unless `plan` fits a batch of len(valid_frames) windows of `rows` rows and `n_frames` frames: as many windows; every
+    warp (0, 0) or within 1 .. valid_frames[k] - 1; every mask that masks something (width > 0) starting inside the batch, below
+    `rows` or `n_frames`.  A mask of width 0 masks nothing wherever it starts, and one that runs past the rows, the frames or
+    valid_frames[k] is clipped there, as clx_specaug_windows clips it."""
+    V = np.asarray(valid_frames, dtype=np.int64).reshape(-1)
+    if len(plan) != V.size:
+        raise ValueError("%s: augment is a plan of %d windows for a batch of %d" % (who, len(plan), V.size))
+    for name, m, limit, what in (("frequency", plan.freq_masks, rows, "rows"), ("time", plan.time_masks, n_frames, "frames")):
+        if np.any((m[..., 1] > 0) & (m[..., 0] >= limit)):
+            raise ValueError("%s: a %s mask of augment starts behind the batch's %d %s" % (who, name, limit, what))
+    c, w = plan.warp[:, 0], plan.warp[:, 1]
+    if np.any(((c != 0) | (w != 0)) & ((c < 1) | (w < 1) | (c >= V) | (w >= V))):
+        raise ValueError("%s: a warp of augment is neither (0, 0) nor within 1 .. valid_frames - 1" % who)
+
+
+class SpecAugmentPlan:
+    """What one SpecAugment.draw gave, a plain value: warp [B, 2] (c, w), freq_masks [B, F, 2] (first row, width), time_masks
+    [B, M, 2] (first output frame, width), int64 arrays, and the fill ("mean" or a float) -- the arguments of
+    Context.specaug_windows, and what read_mel(..., augment=) takes in place of a policy."""
+
+    def __init__(self, warp, freq_masks, time_masks, fill="mean"):
+        self.warp = np.ascontiguousarray(warp, dtype=np.int64).reshape(-1, 2)
+        B = self.warp.shape[0]
+        self.freq_masks = np.ascontiguousarray(freq_masks, dtype=np.int64)
+        self.time_masks = np.ascontiguousarray(time_masks, dtype=np.int64)
+        for name, a in (("freq_masks", self.freq_masks), ("time_masks", self.time_masks)):
+            if a.ndim != 3 or a.shape[0] != B or a.shape[2] != 2:
+                raise ValueError("SpecAugmentPlan: %s must be [%d, n, 2], not %r" % (name, B, tuple(a.shape)))
+        if self.freq_masks.shape[1] > SPECAUG_MAX_MASKS or self.time_masks.shape[1] > SPECAUG_MAX_MASKS:
+            raise ValueError("SpecAugmentPlan: more than %d masks a window" % SPECAUG_MAX_MASKS)
+        if min(self.warp.min(initial=0), self.freq_masks.min(initial=0), self.time_masks.min(initial=0)) < 0:
+            raise ValueError("SpecAugmentPlan: a negative entry")
+        mean, value = _specaug_fill(fill, "SpecAugmentPlan")
+        self.fill = "mean" if mean else value
+
+    def __len__(self):
+        return self.warp.shape[0]
+
+    def __repr__(self):
+        return "SpecAugmentPlan(%d windows, %d frequency masks, %d time masks, fill=%r)" % (
+            len(self), self.freq_masks.shape[1], self.time_masks.shape[1], self.fill)
+
+    def __eq__(self, other):
+        return isinstance(other, SpecAugmentPlan) and self.fill == other.fill and np.array_equal(self.warp, other.warp) \
+            and np.array_equal(self.freq_masks, other.freq_masks) and np.array_equal(self.time_masks, other.time_masks)
+
+    __hash__ = None
+
+
+class SpecAugment:
+    """The SpecAugment policy of read_mel(..., augment=): a time warp, frequency masks and time masks per window, drawn on the host
+    by numpy from `seed` and applied by one clx_specaug_windows call (claxon_hip.h has what a warp and a mask do to the cells).
+    A plain value; draw() gives the SpecAugmentPlan of one batch.  The rule is this library's own, in the spirit of lhotse's
+    SpecAugment (whose defaults these are); it is not lhotse's random stream and gives other draws from the same seed.
+
+    draw(valid_frames, rows): a Generator, numpy.random.default_rng(seed), made once by the constructor, gives for every window
+    in turn, V its valid frames, 3 + 2 freq_masks + 2 time_masks uniform doubles u in [0, 1) in this order, all of them whether
+    they are used or not (so a window's draws do not depend on the windows before it being short):
+      skip      u0 >= p: the window is left alone -- warp (0, 0), every mask of width 0.
+      warp      W = time_warp.  W == 0 or V < 2 W + 2: the window is too short, no warp.  Otherwise c = W + 1 + floor(u1 (V - 2 W - 1))
+                lies in [W + 1, V - W - 1] and w = c - W + floor(u2 (2 W + 1)) in [c - W, c + W], hence both in [1, V - 1].  (w == c
+                is a warp that copies.)
+      freq      mask i: width = floor(u (min(freq_width, rows) + 1)) in [0, min(freq_width, rows)], then first =
+                floor(u' (rows - width + 1)) in [0, rows - width].
+      time      a budget of floor(max_time_fraction V) frames.  Mask i: width = floor(u (min(time_width, V) + 1)), cut to what is
+                left of the budget, which it then uses up; first = floor(u' (V - width + 1)) in [0, V - width].  The widths of a
+                window's time masks therefore add up to at most max_time_fraction V frames, and so do the frames they cover.
+    ValueError for counts outside 0..32, negative widths, a p or max_time_fraction outside [0, 1] and a fill that is neither
+    "mean" nor a finite number."""
+
+    def __init__(self, time_warp=80, freq_masks=2, freq_width=27, time_masks=10, time_width=100, max_time_fraction=0.15, p=0.9, fill="mean",
+                 seed=None):
+        for name, v, hi in (("time_warp", time_warp, (1 << 30) - 1), ("freq_masks", freq_masks, SPECAUG_MAX_MASKS), ("freq_width", freq_width, (1 << 31) - 1),
+                            ("time_masks", time_masks, SPECAUG_MAX_MASKS), ("time_width", time_width, (1 << 31) - 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= hi:
+                raise ValueError("SpecAugment: %s must be a whole number in 0..%d, not %r" % (name, hi, v))
+        for name, v in (("max_time_fraction", max_time_fraction), ("p", p)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError("SpecAugment: %s must be a number in [0, 1], not %r" % (name, v))
+        mean, value = _specaug_fill(fill, "SpecAugment")
+        self.time_warp, self.freq_masks, self.freq_width = int(time_warp), int(freq_masks), int(freq_width)
+        self.time_masks, self.time_width = int(time_masks), int(time_width)
+        self.max_time_fraction, self.p = float(max_time_fraction), float(p)
+        self.fill = "mean" if mean else value
+        self.seed = seed
+        self._rng = np.random.default_rng(seed)
+
+    def __repr__(self):
+        return "SpecAugment(time_warp=%d, freq_masks=%d, freq_width=%d, time_masks=%d, time_width=%d, max_time_fraction=%r, p=%r, fill=%r, seed=%r)" % (
+            self.time_warp, self.freq_masks, self.freq_width, self.time_masks, self.time_width, self.max_time_fraction, self.p, self.fill, self.seed)
+
+    def draw(self, valid_frames, rows):
+        """The plan of one batch: valid_frames [B] whole numbers from 0 up, rows the batch's rows (1..256)."""
+        vf = np.asarray(valid_frames).reshape(-1)
+        if vf.size and (vf.dtype.kind not in "iu" or int(vf.min()) < 0 or int(vf.max()) >= 1 << 31):
+            raise ValueError("SpecAugment.draw: valid_frames must hold whole numbers in 0..2^31 - 1")
+        if isinstance(rows, bool) or int(rows) != rows or not 1 <= int(rows) <= 256:
+            raise ValueError("SpecAugment.draw: rows must be 1..256, not %r" % (rows,))
+        rows, B, F, M, W = int(rows), vf.size, self.freq_masks, self.time_masks, self.time_warp
+        warp = np.zeros((B, 2), dtype=np.int64)
+        fm = np.zeros((B, F, 2), dtype=np.int64)
+        tm = np.zeros((B, M, 2), dtype=np.int64)
+        for k in range(B):
+            V = int(vf[k])
+            u = self._rng.random(3 + 2 * F + 2 * M)
+            if u[0] >= self.p:
+                continue
+            if W > 0 and V >= 2 * W + 2:
+                c = W + 1 + int(u[1] * (V - 2 * W - 1))
+                warp[k] = (c, c - W + int(u[2] * (2 * W + 1)))
+            for i in range(F):
+                width = int(u[3 + 2 * i] * (min(self.freq_width, rows) + 1))
+                fm[k, i] = (int(u[4 + 2 * i] * (rows - width + 1)), width)
+            left = int(self.max_time_fraction * V)
+            for i in range(M):
+                width = min(int(u[3 + 2 * F + 2 * i] * (min(self.time_width, V) + 1)), left)
+                left -= width
+                tm[k, i] = (int(u[4 + 2 * F + 2 * i] * (V - width + 1)), width)
+        return SpecAugmentPlan(warp, fm, tm, self.fill)
+
+
 # ---- a second recording behind the windows ----------------------------------------------------------------------------------------
 
 class Add:
@@ -2357,7 +2568,7 @@ class StreamSet:
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -2383,9 +2594,22 @@ class StreamSet:
         crop.  valid and valid_frames are the signal's.
 
         With reverb=Reverb(...) the Reverb goes to that read() too (starts and taps counted at spec.sample_rate), in front of the
-        Add: the features are those of the reverberant, then noisy, waveform."""
+        Add: the features are those of the reverberant, then noisy, waveform.
+
+        With augment=SpecAugment(...) or a SpecAugmentPlan the features are then warped in time and masked (SpecAugment): one
+        clx_specaug_windows call, the last step -- behind the spec's own launches, a ranged spec's range step and normalize=, so
+        that a CMVN batch masked with fill=0.0 is masked with its mean.  A policy is drawn from the call's valid_frames and
+        n_out rows (SpecAugment.draw); a plan must have B windows, warps that are (0, 0) or within 1 .. valid_frames[k] - 1, and
+        every mask of a width above 0 must start below n_out rows or n_frames frames (a width of 0 masks nothing wherever it starts;
+        a mask that runs past the end is clipped): ValueError otherwise, and for an augment that is neither.  The step is out of
+        place: the tensor returned is a second one, and the one it was made from is released when the call returns, like read()'s
+        scratch.  As with every launch here, on torch's default stream the work goes to the context's own stream, which torch's
+        stream is not ordered against: wait (torch.cuda.synchronize()) before the next torch operation on the device.
+        valid_frames does not change, and the frames behind them keep what they held.  augment=None is the call without the argument."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
+        if augment is not None and not isinstance(augment, (SpecAugment, SpecAugmentPlan)):
+            raise ValueError("read_mel: augment must be a SpecAugment, a SpecAugmentPlan or None, not %r" % (augment,))
         if add is not None and not isinstance(add, Add):
             raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
         if reverb is not None and not isinstance(reverb, Reverb):
@@ -2420,6 +2644,11 @@ class StreamSet:
         vf = spec.valid_frames(valid, n_frames)
         if normalize is not None:
             self.ctx.norm_windows(out, vf, _LAYOUTS[layout], normalize)
+        if augment is not None:
+            plan = augment.draw(vf, spec.n_out) if isinstance(augment, SpecAugment) else augment
+            _specaug_fit(plan, vf, spec.n_out, n_frames, "read_mel")
+            if B and n_frames:
+                out = self.ctx.specaug_windows(out, vf, _LAYOUTS[layout], plan.warp, plan.freq_masks, plan.time_masks, plan.fill)
         return out, torch.from_numpy(vf)
 
 

@@ -17,6 +17,7 @@
 #include "clx_add.hip"
 #include "clx_reverb.hip"
 #include "clx_reverb_fft.hip"
+#include "clx_specaug.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -303,6 +304,13 @@ struct clx_ctx {
     void* d_rvf_tw = nullptr;
     std::vector<void*> rvf_old_dev, rvf_old_host;
     hipEvent_t ev_rvf_up = nullptr, ev_rvf_done = nullptr; bool rvf_used = false;
+    // clx_specaug_windows: the call's table (V, the warp pairs and the clipped masks per window; behind them on the device the
+    // fills) with its pinned staging and its two events, by the same rules (the capacity counted in 32-bit words: the masks of
+    // a call are as many as it says), and the table of the call's double partial sums (device only)
+    uint32_t* d_sa = nullptr; uint32_t* h_sa = nullptr; size_t sa_cap = 0;
+    double* d_sa_part = nullptr; size_t sa_part_cap = 0;
+    std::vector<void*> sa_old_dev, sa_old_host;
+    hipEvent_t ev_sa_up = nullptr, ev_sa_done = nullptr; bool sa_used = false;
 };
 
 struct clx_mel_spec {
@@ -514,6 +522,12 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->rvf_old_dev.push_back(ctx->d_rvf_tw); ctx->rvf_old_host.push_back(ctx->h_rvf);
     for (void* p : ctx->rvf_old_dev) if (p) (void)hipFree(p);
     for (void* p : ctx->rvf_old_host) if (p) (void)hipHostFree(p);
+    if (ctx->sa_used) (void)hipEventSynchronize(ctx->ev_sa_done);
+    if (ctx->ev_sa_up) (void)hipEventDestroy(ctx->ev_sa_up);
+    if (ctx->ev_sa_done) (void)hipEventDestroy(ctx->ev_sa_done);
+    ctx->sa_old_dev.push_back(ctx->d_sa); ctx->sa_old_dev.push_back(ctx->d_sa_part); ctx->sa_old_host.push_back(ctx->h_sa);
+    for (void* p : ctx->sa_old_dev) if (p) (void)hipFree(p);
+    for (void* p : ctx->sa_old_host) if (p) (void)hipHostFree(p);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2031,6 +2045,65 @@ extern "C" int clx_reverb_windows_fft(clx_ctx* ctx, const void* d_data, size_t n
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_rvf_done, stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_specaug_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                   uint32_t layout, const uint32_t* warp, const uint32_t* fmasks, const uint32_t* tmasks,
+                                   const clx_specaug_opts* opts, void* d_fill, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_specaug_plan pl;
+    const char* why = clx_specaug_check(d_in, d_out, n_windows, rows, T, valid, layout, warp, fmasks, tmasks, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!ctx->ev_sa_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_sa_up, hipEventDisableTiming));
+    if (!ctx->ev_sa_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_sa_done, hipEventDisableTiming));
+    const size_t words = (size_t)pl.table_words, words_dev = words + n_windows;       // (the fills behind this call's table)
+    const bool grow_tab = words_dev > ctx->sa_cap, grow_part = pl.partials > ctx->sa_part_cap;
+    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
+        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
+        double* d = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc specaug partial sums")) return CLX_API_ERROR;
+        if (ctx->d_sa_part) ctx->sa_old_dev.push_back(ctx->d_sa_part);
+        ctx->d_sa_part = d; ctx->sa_part_cap = want;
+    }
+    if (grow_tab) {
+        const size_t want = words_dev + words_dev / 2 + 64;
+        uint32_t* d = nullptr; uint32_t* h = nullptr;
+        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc specaug table")) return CLX_API_ERROR;
+        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc specaug table")) { (void)hipFree(d); return CLX_API_ERROR; }
+        if (ctx->d_sa) { ctx->sa_old_dev.push_back(ctx->d_sa); ctx->sa_old_host.push_back(ctx->h_sa); }
+        ctx->d_sa = d; ctx->h_sa = h; ctx->sa_cap = want;
+    }
+    if (ctx->sa_used) {
+        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_sa_up));     // (the upload only: the earlier launch itself is not waited for)
+        if (!grow_tab || (!grow_part && pl.mean)) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_sa_done, 0));
+    }
+    const uint32_t F = fmasks ? opts->n_freq_masks : 0u, M = tmasks ? opts->n_time_masks : 0u;
+    clx_specaug_fill_table(ctx->h_sa, n_windows, rows, valid, warp, fmasks, F, tmasks, M);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sa, ctx->h_sa, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_sa_up, stream));
+    ctx->sa_used = true;                                       // (from here on the staging and the tables are in use)
+    if (pl.mean) {
+        const float* x = (const float*)d_in;
+        if (pl.tc)
+            hipLaunchKernelGGL(clx_k_norm_sum_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_sa,
+                               ctx->d_sa_part, rows, T, pl.n_chunks, pl.n_groups);
+        else
+            hipLaunchKernelGGL(clx_k_norm_sum, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_sa,
+                               ctx->d_sa_part, rows, T, pl.n_chunks, (uint64_t)n_windows * rows * pl.n_chunks);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(clx_k_specaug_fill, dim3(pl.fill_blocks), dim3(clx_specaug::kThreads), 0, stream, (const uint32_t*)ctx->d_sa,
+                           (const double*)ctx->d_sa_part, (float*)(ctx->d_sa + words), (uint32_t)n_windows, rows, pl.n_chunks);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(clx_k_specaug, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_specaug::kThreads), 0, stream, (const uint32_t*)d_in,
+                       (uint32_t*)d_out, (const uint32_t*)ctx->d_sa, (float*)d_fill, (uint32_t)n_windows, rows, T, F, M, pl.mean,
+                       opts->fill_mean ? 0.f : opts->fill, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_sa_done, stream));
     return CLX_OK;
 }
 

@@ -811,6 +811,52 @@ typedef struct { uint32_t keep_power, reserved[3]; } clx_reverb_fft_opts;
 int  clx_reverb_windows_fft(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
                             const void* d_ir, size_t n_ir, uint32_t K, const uint32_t* ir_len, const int32_t* ir_index,
                             uint32_t layout, const clx_reverb_fft_opts* opts, void* d_out, void* d_gains, void* stream);
+/* SpecAugment of a dense float32 feature batch, out of place on the device: a time warp about one frame, frequency masks and time
+ * masks, the last step of the usual speech training recipe.  d_in is [n_windows][rows][T] (CLX_WINDOW_CT) or [n_windows][T][rows]
+ * (CLX_WINDOW_TC), rows in 1..256, and is never written; d_out has the same shape and layout and receives every cell; d_out ==
+ * d_in is refused.  Window k has V = valid[k] <= T live frames.  With x[r][t] the cells of d_in and y[r][t] those of d_out:
+ *
+ *   padding    a cell at t >= V is the input's word, whatever it is: copied, never interpreted, never warped, never masked, and
+ *              never part of the mean.
+ *   warp       warp (may be NULL: none) is [n_windows][2], the pair (c, w) of window k.  (0, 0) is no warp; otherwise
+ *              1 <= c <= V - 1 and 1 <= w <= V - 1.  Output frames [0, w) are input frames [0, c) resized, output frames [w, V)
+ *              are input frames [c, V) resized, each segment by torch.nn.functional.interpolate(mode="bicubic",
+ *              align_corners=False) along time with the coordinate taken exactly.  For local output frame j of a segment with I
+ *              input and O output frames that starts at input frame b:
+ *                num = (2 j + 1) I - O, den = 2 O (64-bit integers); ix = floor(num / den), which is -1 where num < 0;
+ *                tx = (float)((double)(num - ix den) / (double)den): one double division, one rounding to float32.
+ *                The weights, every operation one float32 rounding, none fused, with near(u) = fl(fl(fl(fl(fl(1.25 u) - 2.25) u) u) + 1)
+ *                and far(u) = fl(fl(fl(fl(fl(fl(-0.75 u) + 3.75) u) - 6) u) + 3) (the cubic convolution with A = -0.75):
+ *                w_0 = far(fl(tx + 1)), w_1 = near(tx), w_2 = near(fl(1 - tx)), w_3 = far(fl(2 - tx)).
+ *                The source frames: s_k = b + clamp(ix - 1 + k, 0, I - 1), k = 0 .. 3: inside the segment, never the other segment,
+ *                the padding or another window.
+ *                y[r][t] = acc after acc = +0.0f; acc = fmaf(w_k, x[r][s_k], acc) for k = 0, 1, 2, 3: four fused steps.
+ *              Where I == O (c == w) the segment's cells are the input's words, copied and not computed, as torch does; a NaN
+ *              next to such a cell stays where it is.
+ *   masks      fmasks (may be NULL) is [n_windows][F][2]: (first_row, width); tmasks (may be NULL) is [n_windows][M][2]:
+ *              (first_frame, width), counted in output (warped) frames.  F = opts->n_freq_masks and M = opts->n_time_masks are at
+ *              most 32.  Time masks are clipped to [0, V), frequency masks to [0, rows) and to the frames t < V.  Width 0 masks
+ *              nothing; masks may overlap.  A masked cell is the fill, whatever the warp would have given: its taps are not read.
+ *   fill       opts->fill_mean == 0: the constant opts->fill (finite).  opts->fill_mean == 1: the window's mean over the live
+ *              cells of the INPUT (before the warp): S_r the sum of (double)x[r][t] over t < V in clx_norm_windows' ORDER with
+ *              n = V, S the sum of S_r in ascending r from +0.0, fill = (float)(S / (double)(V * rows)): one double division, one
+ *              rounding; +0.0 for V == 0.  d_fill (may be NULL) is [n_windows] float32 and receives every window's fill.
+ *   layouts    CT and TC of the same data give the same fill and the same cells, bit for bit.
+ *
+ * valid, warp, fmasks and tmasks are host arrays of 32-bit unsigned words, staged as clx_add_windows stages its arrays -- one
+ * pinned table a call, tables that have to grow replaced before anything is queued, one event behind the upload and one behind
+ * the last launch -- so the call is asynchronous on `stream` (NULL: the context's), returns without waiting for the device and
+ * the arrays may be reused at once.  With fill_mean the row sums wait in a table of n_windows * rows * 2 * ceil(T / 4096) doubles
+ * that the context keeps (clx_norm's sum kernels write it).  No floating-point atomics.  CLX_API_ERROR, each with a
+ * clx_last_error text of its own, for opts == NULL, reserved bits, a fill_mean above 1, a constant fill that is not finite, F or M
+ * above 32, an unknown layout, rows outside 1..256, T above 2^31 - 1 (the frames of a window are counted in 32 bits with one to
+ * spare for ix = -1, and (2 j + 1) I stays below 2^63), a null d_in, d_out or valid, d_out == d_in, a valid[k] > T and a warp pair
+ * outside the ranges above.  n_windows == 0 or T == 0 succeeds and launches nothing.  Not here: warps in frequency, several warp
+ * points per window, other interpolation modes, the drawing of the random plan (that is the caller's: claxon_amd.SpecAugment). */
+typedef struct { uint32_t n_freq_masks, n_time_masks, fill_mean; float fill; uint32_t reserved; } clx_specaug_opts;
+int  clx_specaug_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                         uint32_t layout, const uint32_t* warp, const uint32_t* fmasks, const uint32_t* tmasks,
+                         const clx_specaug_opts* opts, void* d_fill, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
