@@ -246,6 +246,56 @@ struct clx_stream_slot {
 #endif
 static_assert(CLX_SUBMIT_MERGE <= CLX_MAX_MERGE && CLX_SUBMIT_STREAMS * CLX_SUBMIT_MERGE <= CLX_SUBMIT_DEPTH && CLX_SUBMIT_STREAMS <= 6, "merge width");
 
+// The per-call scratch of one window entry point: a staged table (the call's table on the device and its pinned staging), the
+// device-only buffers beside it (the double partial sums, clx_reverb_windows_fft's workspace: the kernels write them before they
+// read them) and the two events that hand them from one call to the next.  The calls are asynchronous and those of one context may
+// go to different streams, so:
+//  - a buffer that has to grow is replaced before the call queues anything, and the one it replaces is kept (old_dev, old_host)
+//    until clx_destroy: an earlier call's launch, on whichever stream, may still read it, and freeing it would wait for the device;
+//  - ev_up is behind the last table upload: the host waits for it (for the upload only, not for the earlier launch) before it
+//    rewrites the staging.  A call that replaced the table has a staging nobody reads and does not wait;
+//  - ev_done is behind the last launch: the call's stream (not the host) waits for it before anything rewrites what that launch
+//    may read.  Only a call that replaced EVERY buffer it reserved goes without; a reserved buffer that did not grow counts as
+//    kept, one reserved with need 0 included.  Two asymmetries follow, and both are as they have always been:
+//    clx_reverb_windows without keep_power reserves 0 partial sums and so always waits, even when its table grew;
+//    clx_specaug_windows with a constant fill reserves no partial sums at all and so waits only when its table was kept.
+// An entry point calls begin() before it fills the staging, uploaded() behind its hipMemcpyAsync of the table and done() behind
+// its last launch; clx_destroy calls release().  Needs and capacities of the table are counted in the set's own unit (windows,
+// 32-bit words or bytes).
+struct clx_call_scratch {
+    static constexpr size_t kNone = ~(size_t)0;                // begin(): the call does not reserve that device-only buffer
+    struct Dev { void* p = nullptr; size_t cap = 0; };
+    const char* const name;                                    // in the text of a failed allocation: "hipMalloc <name> table"
+    const size_t slack, dev_unit, host_unit;                   // the table grows to need + need / 2 + slack units: dev_unit bytes each on the device, host_unit pinned
+    void* d = nullptr; void* h = nullptr; size_t cap = 0;      // the staged table
+    Dev part, ws;                                              // the partial sums (cap in doubles) and the workspace (in bytes)
+    std::vector<void*> old_dev, old_host;
+    hipEvent_t ev_up = nullptr, ev_done = nullptr; bool used = false;
+
+    clx_call_scratch(const char* name_, size_t slack_, size_t dev_unit_, size_t host_unit_)
+        : name(name_), slack(slack_), dev_unit(dev_unit_), host_unit(host_unit_) {}
+    // the events, then growth (the workspace, the partial sums, the table), then the waits; CLX_API_ERROR with ctx->last_error set
+    int begin(clx_ctx* ctx, hipStream_t stream, size_t need, size_t partials = kNone, size_t ws_bytes = kNone);
+    hipError_t uploaded(hipStream_t stream) {
+        const hipError_t e = hipEventRecord(ev_up, stream);
+        if (e == hipSuccess) used = true;                      // (from here on the staging and the tables are in use)
+        return e;
+    }
+    hipError_t done(hipStream_t stream) { return hipEventRecord(ev_done, stream); }
+    void release() {
+        if (used) (void)hipEventSynchronize(ev_done);
+        if (ev_up) (void)hipEventDestroy(ev_up);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        for (void* p : { d, part.p, ws.p }) old_dev.push_back(p);
+        old_host.push_back(h);
+        for (void* p : old_dev) if (p) (void)hipFree(p);
+        for (void* p : old_host) if (p) (void)hipHostFree(p);
+    }
+private:
+    bool alloc_ok(clx_ctx* ctx, hipError_t e, const char* call, const char* what) const;
+    bool reserve(clx_ctx* ctx, Dev& b, size_t need, size_t want, size_t unit, const char* what, bool* kept);
+};
+
 struct clx_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -255,62 +305,32 @@ struct clx_ctx {
     // scratch of clx_index_streams_device: kept until clx_destroy, regrown only by a call that needs more than any before (idx_reserve)
     struct IdxBuf { void* p = nullptr; size_t cap = 0; };
     IdxBuf idx_arena, idx_tab, idx_mask, idx_blk, idx_pos, idx_sid, idx_hdr, idx_crc;
-    // scratch of clx_gather_windows: the window table on the device and its pinned staging.  A table that has to grow is replaced
-    // before the call queues anything; the one it replaces may still be read by an earlier call's launch, so it is kept (win_old)
-    // until clx_destroy.  ev_win_up: behind the last table upload (the staging is rewritten only after it); ev_win_done: behind the
-    // last launch (the device table is rewritten only after it, whichever stream that launch went to).
-    clx_win_job* d_win = nullptr; clx_win_job* h_win = nullptr; size_t win_cap = 0;
-    std::vector<void*> win_old_dev, win_old_host;
-    hipEvent_t ev_win_up = nullptr, ev_win_done = nullptr; bool win_used = false;
-    // scratch of clx_resample_windows and clx_mix_windows (one set for both), by the same rules: one table of the call's jobs followed by its rate pairs (rs_cap bytes, on
-    // the device and in pinned staging), and the coefficient tables of every rate pair the context has met (rs_cache: the host copy;
-    // d_rs_coef: the first rs_coef_up floats of it).  A pair's table is written once, behind those in use, so an earlier launch
-    // never reads what an upload writes; a coefficient buffer that has to grow is replaced like a job table (rs_old_dev).
-    void* d_rs = nullptr; void* h_rs = nullptr; size_t rs_cap = 0;
+    // one clx_call_scratch per window entry point (the rules are on the type).  win: clx_gather_windows' table of clx_win_job
+    clx_call_scratch win { "window", 64, sizeof(clx_win_job), sizeof(clx_win_job) };
+    // clx_resample_windows and clx_mix_windows (one set for both; in bytes): the call's jobs followed by its rate pairs.  Beside it the
+    // coefficient tables of every rate pair the context has met (rs_cache: the host copy; d_rs_coef: the first rs_coef_up floats of
+    // it).  A pair's table is written once, behind those in use, so an earlier launch never reads what an upload writes; a
+    // coefficient buffer that has to grow is replaced like a job table (parked in rs.old_dev)
+    clx_call_scratch rs { "resample", 4096, 1, 1 };
     clx_rs_cache rs_cache; float* d_rs_coef = nullptr; size_t rs_coef_cap = 0, rs_coef_up = 0;
     std::vector<uint32_t> rs_call_fs;
-    std::vector<void*> rs_old_dev, rs_old_host;
-    hipEvent_t ev_rs_up = nullptr, ev_rs_done = nullptr; bool rs_used = false;
     // clx_mel_windows: the specs the context owns (each with its tables on the device, written once by clx_mel_create), and the
-    // table of the call's valid_frames with its pinned staging and its two events, by the rules of the window table above
+    // call's table (in 32-bit words): valid_frames per window (centred or ranged: then lim and wmax; reflected: then vlen)
     std::vector<clx_mel_spec*> mel_specs;
-    uint32_t* d_mel = nullptr; uint32_t* h_mel = nullptr; size_t mel_cap = 0;
-    std::vector<void*> mel_old_dev, mel_old_host;
-    hipEvent_t ev_mel_up = nullptr, ev_mel_done = nullptr; bool mel_used = false;
-    // clx_norm_windows: the call's valid[] on the device with its pinned staging and its two events, by the same rules, and the
-    // table of the call's double partial sums (device only: the kernels write it before they read it)
-    uint32_t* d_norm = nullptr; uint32_t* h_norm = nullptr; size_t norm_cap = 0;
-    double* d_norm_part = nullptr; size_t norm_part_cap = 0;
-    std::vector<void*> norm_old_dev, norm_old_host;
-    hipEvent_t ev_norm_up = nullptr, ev_norm_done = nullptr; bool norm_used = false;
-    // clx_add_windows: the call's table (q, Vs, Vn, j per window; behind them on the device the gains) with its pinned staging and
-    // its two events, by the same rules, and the table of the call's double partial sums (device only)
-    void* d_add = nullptr; void* h_add = nullptr; size_t add_cap = 0;
-    double* d_add_part = nullptr; size_t add_part_cap = 0;
-    std::vector<void*> add_old_dev, add_old_host;
-    hipEvent_t ev_add_up = nullptr, ev_add_done = nullptr; bool add_used = false;
-    // clx_reverb_windows: the call's table (clx_add's four arrays, then len and idx per window; behind them on the device the gains)
-    // with its pinned staging and its two events, by the same rules, and the table of the call's double partial sums (device only)
-    void* d_rv = nullptr; void* h_rv = nullptr; size_t rv_cap = 0;
-    double* d_rv_part = nullptr; size_t rv_part_cap = 0;
-    std::vector<void*> rv_old_dev, rv_old_host;
-    hipEvent_t ev_rv_up = nullptr, ev_rv_done = nullptr; bool rv_used = false;
-    // clx_reverb_windows_fft: the same set of its own (the table's capacity counted in bytes: it ends in the call's partition jobs),
-    // the workspace of the segment and partition spectra, kept and grown the way the partial sums are, and the twiddles (written
-    // once, by the first call)
-    void* d_rvf = nullptr; void* h_rvf = nullptr; size_t rvf_cap = 0;
-    double* d_rvf_part = nullptr; size_t rvf_part_cap = 0;
-    void* d_rvf_ws = nullptr; size_t rvf_ws_cap = 0;
+    clx_call_scratch mel { "mel", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    // clx_norm_windows: the call's valid[]
+    clx_call_scratch norm { "norm", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    // clx_add_windows: q, Vs, Vn, j per window; behind them on the device the gains
+    clx_call_scratch add { "add", 64, clx_add::kTableBytesDevice, clx_add::kTableBytes };
+    // clx_reverb_windows: clx_add's four arrays, then len and idx per window; behind them on the device the gains
+    clx_call_scratch rv { "reverb", 64, clx_reverb::kTableBytesDevice, clx_reverb::kTableBytes };
+    // clx_reverb_windows_fft (in bytes): clx_reverb_windows' table, the gains behind it, then the call's partition jobs.  Beside it
+    // the twiddles (written once, by the first call)
+    clx_call_scratch rvf { "reverb", 4096, 1, 1 };
     void* d_rvf_tw = nullptr;
-    std::vector<void*> rvf_old_dev, rvf_old_host;
-    hipEvent_t ev_rvf_up = nullptr, ev_rvf_done = nullptr; bool rvf_used = false;
-    // clx_specaug_windows: the call's table (V, the warp pairs and the clipped masks per window; behind them on the device the
-    // fills) with its pinned staging and its two events, by the same rules (the capacity counted in 32-bit words: the masks of
-    // a call are as many as it says), and the table of the call's double partial sums (device only)
-    uint32_t* d_sa = nullptr; uint32_t* h_sa = nullptr; size_t sa_cap = 0;
-    double* d_sa_part = nullptr; size_t sa_part_cap = 0;
-    std::vector<void*> sa_old_dev, sa_old_host;
-    hipEvent_t ev_sa_up = nullptr, ev_sa_done = nullptr; bool sa_used = false;
+    // clx_specaug_windows (in 32-bit words: the masks of a call are as many as it says): V, the warp pairs and the clipped masks
+    // per window; behind them on the device the fills
+    clx_call_scratch sa { "specaug", 64, sizeof(uint32_t), sizeof(uint32_t) };
 };
 
 struct clx_mel_spec {
@@ -444,6 +464,43 @@ bool hip_ok(clx_ctx* ctx, hipError_t e, const char* what) {
 #define HIP_TRY(ctx, call) do { if (!hip_ok((ctx), (call), #call)) return CLX_API_ERROR; } while (0)
 }  // namespace
 
+// (a failed allocation's text: `call` <name> `what`)
+bool clx_call_scratch::alloc_ok(clx_ctx* ctx, hipError_t e, const char* call, const char* what) const {
+    return e == hipSuccess || hip_ok(ctx, e, (std::string(call) + " " + name + " " + what).c_str());
+}
+
+bool clx_call_scratch::reserve(clx_ctx* ctx, Dev& b, size_t need, size_t want, size_t unit, const char* what, bool* kept) {
+    if (need <= b.cap) { *kept = true; return true; }
+    void* p = nullptr;
+    if (!alloc_ok(ctx, hipMalloc(&p, want * unit), "hipMalloc", what)) return false;
+    if (b.p) old_dev.push_back(b.p);
+    b.p = p; b.cap = want;
+    return true;
+}
+
+int clx_call_scratch::begin(clx_ctx* ctx, hipStream_t stream, size_t need, size_t partials, size_t ws_bytes) {
+    if (!ev_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
+    if (!ev_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+    bool kept = false;                                         // a buffer this call reserved and did not replace
+    if (ws_bytes != kNone && !reserve(ctx, ws, ws_bytes, ws_bytes + ws_bytes / 2, 1, "spectra (the workspace of clx_reverb_windows_fft)", &kept))
+        return CLX_API_ERROR;                                  // (only "reverb" has one)
+    if (partials != kNone && !reserve(ctx, part, partials, partials + partials / 2 + 64, sizeof(double), "partial sums", &kept)) return CLX_API_ERROR;
+    const bool grow_tab = need > cap;
+    if (grow_tab) {
+        const size_t want = need + need / 2 + slack;
+        void* nd = nullptr; void* nh = nullptr;
+        if (!alloc_ok(ctx, hipMalloc(&nd, want * dev_unit), "hipMalloc", "table")) return CLX_API_ERROR;
+        if (!alloc_ok(ctx, hipHostMalloc(&nh, want * host_unit, hipHostMallocDefault), "hipHostMalloc", "table")) { (void)hipFree(nd); return CLX_API_ERROR; }
+        if (d) { old_dev.push_back(d); old_host.push_back(h); }
+        d = nd; h = nh; cap = want;
+    } else kept = true;
+    if (used) {
+        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ev_up));           // (the upload only: the earlier launch itself is not waited for)
+        if (kept) HIP_TRY(ctx, hipStreamWaitEvent(stream, ev_done, 0));
+    }
+    return CLX_OK;
+}
+
 extern "C" void clx_batch_destroy(clx_batch* b);
 
 extern "C" int clx_create(int device, clx_ctx** out) {
@@ -478,56 +535,17 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     }
     for (clx_ctx::IdxBuf* b : { &ctx->idx_arena, &ctx->idx_tab, &ctx->idx_mask, &ctx->idx_blk, &ctx->idx_pos, &ctx->idx_sid, &ctx->idx_hdr, &ctx->idx_crc })
         if (b->p) (void)hipFree(b->p);
-    if (ctx->win_used) (void)hipEventSynchronize(ctx->ev_win_done);
-    if (ctx->ev_win_up) (void)hipEventDestroy(ctx->ev_win_up);
-    if (ctx->ev_win_done) (void)hipEventDestroy(ctx->ev_win_done);
-    ctx->win_old_dev.push_back(ctx->d_win); ctx->win_old_host.push_back(ctx->h_win);
-    for (void* p : ctx->win_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->win_old_host) if (p) (void)hipHostFree(p);
-    if (ctx->rs_used) (void)hipEventSynchronize(ctx->ev_rs_done);
-    if (ctx->ev_rs_up) (void)hipEventDestroy(ctx->ev_rs_up);
-    if (ctx->ev_rs_done) (void)hipEventDestroy(ctx->ev_rs_done);
-    ctx->rs_old_dev.push_back(ctx->d_rs); ctx->rs_old_dev.push_back(ctx->d_rs_coef); ctx->rs_old_host.push_back(ctx->h_rs);
-    for (void* p : ctx->rs_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->rs_old_host) if (p) (void)hipHostFree(p);
-    if (ctx->mel_used) (void)hipEventSynchronize(ctx->ev_mel_done);
-    if (ctx->ev_mel_up) (void)hipEventDestroy(ctx->ev_mel_up);
-    if (ctx->ev_mel_done) (void)hipEventDestroy(ctx->ev_mel_done);
-    ctx->mel_old_dev.push_back(ctx->d_mel); ctx->mel_old_host.push_back(ctx->h_mel);
-    for (void* p : ctx->mel_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->mel_old_host) if (p) (void)hipHostFree(p);
+    ctx->win.release();
+    ctx->rs.old_dev.push_back(ctx->d_rs_coef);                 // (no per-call table, but parked and freed with the set)
+    ctx->rs.release();
+    ctx->mel.release();
     for (clx_mel_spec* sp : ctx->mel_specs) { if (sp->d_tables) (void)hipFree(sp->d_tables); delete sp; }
-    if (ctx->norm_used) (void)hipEventSynchronize(ctx->ev_norm_done);
-    if (ctx->ev_norm_up) (void)hipEventDestroy(ctx->ev_norm_up);
-    if (ctx->ev_norm_done) (void)hipEventDestroy(ctx->ev_norm_done);
-    ctx->norm_old_dev.push_back(ctx->d_norm); ctx->norm_old_dev.push_back(ctx->d_norm_part); ctx->norm_old_host.push_back(ctx->h_norm);
-    for (void* p : ctx->norm_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->norm_old_host) if (p) (void)hipHostFree(p);
-    if (ctx->add_used) (void)hipEventSynchronize(ctx->ev_add_done);
-    if (ctx->ev_add_up) (void)hipEventDestroy(ctx->ev_add_up);
-    if (ctx->ev_add_done) (void)hipEventDestroy(ctx->ev_add_done);
-    ctx->add_old_dev.push_back(ctx->d_add); ctx->add_old_dev.push_back(ctx->d_add_part); ctx->add_old_host.push_back(ctx->h_add);
-    for (void* p : ctx->add_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->add_old_host) if (p) (void)hipHostFree(p);
-    if (ctx->rv_used) (void)hipEventSynchronize(ctx->ev_rv_done);
-    if (ctx->ev_rv_up) (void)hipEventDestroy(ctx->ev_rv_up);
-    if (ctx->ev_rv_done) (void)hipEventDestroy(ctx->ev_rv_done);
-    ctx->rv_old_dev.push_back(ctx->d_rv); ctx->rv_old_dev.push_back(ctx->d_rv_part); ctx->rv_old_host.push_back(ctx->h_rv);
-    for (void* p : ctx->rv_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->rv_old_host) if (p) (void)hipHostFree(p);
-    if (ctx->rvf_used) (void)hipEventSynchronize(ctx->ev_rvf_done);
-    if (ctx->ev_rvf_up) (void)hipEventDestroy(ctx->ev_rvf_up);
-    if (ctx->ev_rvf_done) (void)hipEventDestroy(ctx->ev_rvf_done);
-    ctx->rvf_old_dev.push_back(ctx->d_rvf); ctx->rvf_old_dev.push_back(ctx->d_rvf_part); ctx->rvf_old_dev.push_back(ctx->d_rvf_ws);
-    ctx->rvf_old_dev.push_back(ctx->d_rvf_tw); ctx->rvf_old_host.push_back(ctx->h_rvf);
-    for (void* p : ctx->rvf_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->rvf_old_host) if (p) (void)hipHostFree(p);
-    if (ctx->sa_used) (void)hipEventSynchronize(ctx->ev_sa_done);
-    if (ctx->ev_sa_up) (void)hipEventDestroy(ctx->ev_sa_up);
-    if (ctx->ev_sa_done) (void)hipEventDestroy(ctx->ev_sa_done);
-    ctx->sa_old_dev.push_back(ctx->d_sa); ctx->sa_old_dev.push_back(ctx->d_sa_part); ctx->sa_old_host.push_back(ctx->h_sa);
-    for (void* p : ctx->sa_old_dev) if (p) (void)hipFree(p);
-    for (void* p : ctx->sa_old_host) if (p) (void)hipHostFree(p);
+    ctx->norm.release();
+    ctx->add.release();
+    ctx->rv.release();
+    ctx->rvf.old_dev.push_back(ctx->d_rvf_tw);                 // (the same)
+    ctx->rvf.release();
+    ctx->sa.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1531,27 +1549,15 @@ extern "C" int clx_gather_windows(clx_ctx* ctx, const void* d_src, const uint64_
     if (n_tiles == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_win_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_win_up, hipEventDisableTiming));
-    if (!ctx->ev_win_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_win_done, hipEventDisableTiming));
-    if (n_windows > ctx->win_cap) {                            // a larger table, before anything is queued; the old one is not freed here
-        const size_t want = n_windows + n_windows / 2 + 64;
-        clx_win_job* d = nullptr; clx_win_job* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(clx_win_job)), "hipMalloc window table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(clx_win_job), hipHostMallocDefault), "hipHostMalloc window table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_win) { ctx->win_old_dev.push_back(ctx->d_win); ctx->win_old_host.push_back(ctx->h_win); }
-        ctx->d_win = d; ctx->h_win = h; ctx->win_cap = want;
-    } else if (ctx->win_used) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_win_up));     // (the upload only: the earlier launch itself is not waited for)
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_win_done, 0));
-    }
-    clx_window_fill(ctx->h_win, src_first, valid, n_windows);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_win, ctx->h_win, n_windows * sizeof(clx_win_job), hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_win_up, stream));
-    ctx->win_used = true;                                      // (from here on the staging and the table are in use)
+    clx_call_scratch& s = ctx->win;
+    if (s.begin(ctx, stream, n_windows) != CLX_OK) return CLX_API_ERROR;
+    clx_window_fill((clx_win_job*)s.h, src_first, valid, n_windows);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, n_windows * sizeof(clx_win_job), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
     hipLaunchKernelGGL(clx_k_window, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_win::kThreads), 0, stream, (const uint32_t*)d_src,
-                       (const clx_win_job*)ctx->d_win, n_tiles, window_len, channels, layout, (uint32_t*)d_out);
+                       (const clx_win_job*)s.d, n_tiles, window_len, channels, layout, (uint32_t*)d_out);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_win_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -1562,22 +1568,11 @@ static int clx_rs_submit(clx_ctx* ctx, const void* d_src, const uint64_t* src_fi
                          uint32_t out_rate, uint32_t window_len, uint32_t channels, uint32_t layout, void* d_out, void* stream_, uint32_t n_tiles) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_rs_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rs_up, hipEventDisableTiming));
-    if (!ctx->ev_rs_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rs_done, hipEventDisableTiming));
     const size_t n_rates = 1 + ctx->rs_call_fs.size();
     const size_t bytes = n_windows * sizeof(clx_rs_job) + n_rates * sizeof(clx_rs_rate);       // (the jobs, then the rate pairs: both 8-byte aligned)
-    if (bytes > ctx->rs_cap) {                                 // a larger table, before anything is queued; the old one is not freed here
-        const size_t want = bytes + bytes / 2 + 4096;
-        void* d = nullptr; void* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&d, want), "hipMalloc resample table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc(&h, want, hipHostMallocDefault), "hipHostMalloc resample table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_rs) { ctx->rs_old_dev.push_back(ctx->d_rs); ctx->rs_old_host.push_back(ctx->h_rs); }
-        ctx->d_rs = d; ctx->h_rs = h; ctx->rs_cap = want;
-    } else if (ctx->rs_used) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_rs_up));      // (the upload only: the earlier launch itself is not waited for)
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_rs_done, 0));
-    }
-    clx_rs_job* h_jobs = (clx_rs_job*)ctx->h_rs;
+    clx_call_scratch& s = ctx->rs;
+    if (s.begin(ctx, stream, bytes) != CLX_OK) return CLX_API_ERROR;
+    clx_rs_job* h_jobs = (clx_rs_job*)s.h;
     clx_rs_rate* h_rates = (clx_rs_rate*)(h_jobs + n_windows);
     if (src_channels)
         clx_mix_fill(&ctx->rs_cache, h_jobs, h_rates, ctx->rs_call_fs, src_first, src_t0, src_n, out_t0, valid, src_rate, src_channels, n_windows, out_rate);
@@ -1589,7 +1584,7 @@ static int clx_rs_submit(clx_ctx* ctx, const void* d_src, const uint64_t* src_fi
         const size_t want = coef.size() + coef.size() / 2 + 4096;
         float* d = nullptr;
         if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(float)), "hipMalloc resample coefficients")) return CLX_API_ERROR;
-        if (ctx->d_rs_coef) ctx->rs_old_dev.push_back(ctx->d_rs_coef);
+        if (ctx->d_rs_coef) s.old_dev.push_back(ctx->d_rs_coef);
         ctx->d_rs_coef = d; ctx->rs_coef_cap = want; ctx->rs_coef_up = 0;
     }
     if (coef.size() > ctx->rs_coef_up) {
@@ -1597,10 +1592,9 @@ static int clx_rs_submit(clx_ctx* ctx, const void* d_src, const uint64_t* src_fi
                                hipMemcpyHostToDevice));
         ctx->rs_coef_up = coef.size();
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rs, ctx->h_rs, bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_rs_up, stream));
-    ctx->rs_used = true;                                       // (from here on the staging and the table are in use)
-    const clx_rs_job* d_jobs = (const clx_rs_job*)ctx->d_rs;
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    const clx_rs_job* d_jobs = (const clx_rs_job*)s.d;
     if (src_channels)
         hipLaunchKernelGGL(clx_k_mix, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_rs::kThreads), 0, stream, (const float*)d_src, d_jobs,
                            (const clx_rs_rate*)(d_jobs + n_windows), (const float*)ctx->d_rs_coef, n_tiles, window_len, channels, layout, (float*)d_out);
@@ -1608,7 +1602,7 @@ static int clx_rs_submit(clx_ctx* ctx, const void* d_src, const uint64_t* src_fi
         hipLaunchKernelGGL(clx_k_resample, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_rs::kThreads), 0, stream, (const float*)d_src, d_jobs,
                            (const clx_rs_rate*)(d_jobs + n_windows), (const float*)ctx->d_rs_coef, n_tiles, window_len, channels, layout, (float*)d_out);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_rs_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -1708,7 +1702,7 @@ extern "C" void clx_mel_destroy(clx_ctx* ctx, clx_mel_spec* spec) {
     if (it == ctx->mel_specs.end()) return;                    // (not this context's, or destroyed already)
     ctx->mel_specs.erase(it);
     (void)hipSetDevice(ctx->device);
-    if (ctx->mel_used) (void)hipEventSynchronize(ctx->ev_mel_done);   // (the last launch, hence every launch that may read the tables)
+    if (ctx->mel.used) (void)hipEventSynchronize(ctx->mel.ev_done);   // (the last launch, hence every launch that may read the tables)
     if (spec->d_tables) (void)hipFree(spec->d_tables);
     delete spec;
 }
@@ -1723,57 +1717,46 @@ extern "C" int clx_mel_windows(clx_ctx* ctx, const clx_mel_spec* spec, const voi
     if (n_groups == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_mel_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_up, hipEventDisableTiming));
-    if (!ctx->ev_mel_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_mel_done, hipEventDisableTiming));
     const bool is_c = clx_mel_is_c(spec->t), is_r = clx_mel_is_r(spec->t);
     const size_t words = is_c ? 3u * n_windows : is_r ? 2u * n_windows : n_windows;   // (valid_frames; centred or ranged: also lim and wmax; reflected: also vlen)
-    if (words > ctx->mel_cap) {                                // a larger table, before anything is queued; the old one is not freed here
-        const size_t want = words + words / 2 + 64;
-        uint32_t* d = nullptr; uint32_t* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc mel table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc mel table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_mel) { ctx->mel_old_dev.push_back(ctx->d_mel); ctx->mel_old_host.push_back(ctx->h_mel); }
-        ctx->d_mel = d; ctx->h_mel = h; ctx->mel_cap = want;
-    } else if (ctx->mel_used) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_mel_up));     // (the upload only: the earlier launch itself is not waited for)
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_mel_done, 0));
-    }
-    if (is_c) clx_mel_fill_c(ctx->h_mel, valid, n_windows, spec->t, window_len, n_frames);
-    else if (is_r) clx_mel_fill_r(ctx->h_mel, valid, n_windows, spec->t, n_frames);
-    else clx_mel_fill(ctx->h_mel, valid, n_windows, spec->t.hop, n_frames, 0u, clx_mel_whole(spec->t));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mel, ctx->h_mel, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_up, stream));
-    ctx->mel_used = true;                                      // (from here on the staging and the table are in use)
+    clx_call_scratch& s = ctx->mel;
+    if (s.begin(ctx, stream, words) != CLX_OK) return CLX_API_ERROR;
+    uint32_t* const h_mel = (uint32_t*)s.h; uint32_t* const d_mel = (uint32_t*)s.d;
+    if (is_c) clx_mel_fill_c(h_mel, valid, n_windows, spec->t, window_len, n_frames);
+    else if (is_r) clx_mel_fill_r(h_mel, valid, n_windows, spec->t, n_frames);
+    else clx_mel_fill(h_mel, valid, n_windows, spec->t.hop, n_frames, 0u, clx_mel_whole(spec->t));
+    HIP_TRY(ctx, hipMemcpyAsync(d_mel, h_mel, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
     if (is_r && clx_mel_is_q(spec->t)) {
         hipLaunchKernelGGL(clx_k_mel_qr, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                           (const uint32_t*)ctx->d_mel, (uint32_t)n_windows, spec->dev, clx_mel_fargs(spec->t), spec->qdev, clx_mel_origin(spec->t),
+                           (const uint32_t*)d_mel, (uint32_t)n_windows, spec->dev, clx_mel_fargs(spec->t), spec->qdev, clx_mel_origin(spec->t),
                            n_groups, window_len, n_frames, layout, (float*)d_out);
     } else if (is_r) {
         hipLaunchKernelGGL(clx_k_mel_fr, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                           (const uint32_t*)ctx->d_mel, (uint32_t)n_windows, spec->dev, clx_mel_fargs(spec->t), clx_mel_origin(spec->t), n_groups,
+                           (const uint32_t*)d_mel, (uint32_t)n_windows, spec->dev, clx_mel_fargs(spec->t), clx_mel_origin(spec->t), n_groups,
                            window_len, n_frames, layout, (float*)d_out);
     } else if (clx_mel_is_q(spec->t)) {
         hipLaunchKernelGGL(clx_k_mel_q, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                           (const uint32_t*)ctx->d_mel, spec->dev, clx_mel_fargs(spec->t), spec->qdev, n_groups, window_len, n_frames, layout,
+                           (const uint32_t*)d_mel, spec->dev, clx_mel_fargs(spec->t), spec->qdev, n_groups, window_len, n_frames, layout,
                            (float*)d_out);
     } else if (clx_mel_is_f(spec->t)) {
         hipLaunchKernelGGL(clx_k_mel_f, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                           (const uint32_t*)ctx->d_mel, spec->dev, clx_mel_fargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
+                           (const uint32_t*)d_mel, spec->dev, clx_mel_fargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
     } else if (!is_c) {
         hipLaunchKernelGGL(clx_k_mel, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                           (const uint32_t*)ctx->d_mel, spec->dev, n_groups, window_len, n_frames, layout, (float*)d_out);
+                           (const uint32_t*)d_mel, spec->dev, n_groups, window_len, n_frames, layout, (float*)d_out);
     } else {
         hipLaunchKernelGGL(clx_k_mel_c, dim3((unsigned)(n_windows * n_groups)), dim3(clx_mel::kThreads), 0, stream, (const float*)d_audio,
-                           ctx->d_mel, (uint32_t)n_windows, spec->dev, clx_mel_cargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
+                           d_mel, (uint32_t)n_windows, spec->dev, clx_mel_cargs(spec->t), n_groups, window_len, n_frames, layout, (float*)d_out);
         if (n_tiles) {                                         // the range step, in place, behind it
             HIP_TRY(ctx, hipGetLastError());
             hipLaunchKernelGGL(clx_k_mel_range, dim3((unsigned)(n_windows * n_tiles)), dim3(clx_mel::kThreads), 0, stream, (float*)d_out,
-                               (const uint32_t*)(ctx->d_mel + 2u * n_windows), (uint64_t)spec->t.n_mels * n_frames, n_tiles,
+                               (const uint32_t*)(d_mel + 2u * n_windows), (uint64_t)spec->t.n_mels * n_frames, n_tiles,
                                spec->t.range_width, spec->t.shift, spec->t.scale);
         }
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_mel_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -1786,57 +1769,37 @@ extern "C" int clx_norm_windows(clx_ctx* ctx, void* d_data, size_t n_windows, ui
     if (pl.n_chunks == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_norm_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_norm_up, hipEventDisableTiming));
-    if (!ctx->ev_norm_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_norm_done, hipEventDisableTiming));
-    const bool grow_tab = n_windows > ctx->norm_cap, grow_part = pl.partials > ctx->norm_part_cap;
-    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
-        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
-        double* d = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc norm partial sums")) return CLX_API_ERROR;
-        if (ctx->d_norm_part) ctx->norm_old_dev.push_back(ctx->d_norm_part);
-        ctx->d_norm_part = d; ctx->norm_part_cap = want;
-    }
-    if (grow_tab) {
-        const size_t want = n_windows + n_windows / 2 + 64;
-        uint32_t* d = nullptr; uint32_t* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc norm table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc norm table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_norm) { ctx->norm_old_dev.push_back(ctx->d_norm); ctx->norm_old_host.push_back(ctx->h_norm); }
-        ctx->d_norm = d; ctx->h_norm = h; ctx->norm_cap = want;
-    }
-    if (ctx->norm_used) {
-        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_norm_up));   // (the upload only: the earlier launch itself is not waited for)
-        if (!grow_tab || !grow_part) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_norm_done, 0));
-    }
-    memcpy(ctx->h_norm, valid, n_windows * sizeof(uint32_t));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_norm, ctx->h_norm, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_norm_up, stream));
-    ctx->norm_used = true;                                     // (from here on the staging and the tables are in use)
+    clx_call_scratch& s = ctx->norm;
+    if (s.begin(ctx, stream, n_windows, (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;
+    uint32_t* const d_norm = (uint32_t*)s.d; double* const d_norm_part = (double*)s.part.p;
+    memcpy(s.h, valid, n_windows * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
     const uint64_t units = (uint64_t)n_windows * rows * pl.n_chunks;
     const float* x = (const float*)d_data;
     if (pl.tc) {
-        hipLaunchKernelGGL(clx_k_norm_sum_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
-                           ctx->d_norm_part, rows, T, pl.n_chunks, pl.n_groups);
+        hipLaunchKernelGGL(clx_k_norm_sum_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)d_norm,
+                           d_norm_part, rows, T, pl.n_chunks, pl.n_groups);
         if (opts->var) {
             HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(clx_k_norm_sq_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
-                               ctx->d_norm_part, rows, T, pl.n_chunks, pl.n_groups);
+            hipLaunchKernelGGL(clx_k_norm_sq_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)d_norm,
+                               d_norm_part, rows, T, pl.n_chunks, pl.n_groups);
         }
     } else {
-        hipLaunchKernelGGL(clx_k_norm_sum, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
-                           ctx->d_norm_part, rows, T, pl.n_chunks, units);
+        hipLaunchKernelGGL(clx_k_norm_sum, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)d_norm,
+                           d_norm_part, rows, T, pl.n_chunks, units);
         if (opts->var) {
             HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(clx_k_norm_sq, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_norm,
-                               ctx->d_norm_part, rows, T, pl.n_chunks, units);
+            hipLaunchKernelGGL(clx_k_norm_sq, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)d_norm,
+                               d_norm_part, rows, T, pl.n_chunks, units);
         }
     }
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(clx_k_norm_apply, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_norm::kThreads), 0, stream, (float*)d_data,
-                       (const uint32_t*)ctx->d_norm, (const double*)ctx->d_norm_part, (float*)d_stats, *opts, rows, T, pl.n_chunks, pl.tc,
+                       (const uint32_t*)d_norm, (const double*)d_norm_part, (float*)d_stats, *opts, rows, T, pl.n_chunks, pl.tc,
                        pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_norm_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -1850,48 +1813,28 @@ extern "C" int clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uin
     if (pl.n_chunks == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_add_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_add_up, hipEventDisableTiming));
-    if (!ctx->ev_add_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_add_done, hipEventDisableTiming));
-    const bool grow_tab = n_windows > ctx->add_cap, grow_part = pl.partials > ctx->add_part_cap;
-    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
-        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
-        double* d = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc add partial sums")) return CLX_API_ERROR;
-        if (ctx->d_add_part) ctx->add_old_dev.push_back(ctx->d_add_part);
-        ctx->d_add_part = d; ctx->add_part_cap = want;
-    }
-    if (grow_tab) {
-        const size_t want = n_windows + n_windows / 2 + 64;
-        void* d = nullptr; void* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&d, want * clx_add::kTableBytesDevice), "hipMalloc add table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc(&h, want * clx_add::kTableBytes, hipHostMallocDefault), "hipHostMalloc add table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_add) { ctx->add_old_dev.push_back(ctx->d_add); ctx->add_old_host.push_back(ctx->h_add); }
-        ctx->d_add = d; ctx->h_add = h; ctx->add_cap = want;
-    }
-    if (ctx->add_used) {
-        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_add_up));    // (the upload only: the earlier launch itself is not waited for)
-        if (!grow_tab || !grow_part) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_add_done, 0));
-    }
-    clx_add_fill(ctx->h_add, n_windows, valid, noise_valid, noise_index, snr_db);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_add, ctx->h_add, n_windows * clx_add::kTableBytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_add_up, stream));
-    ctx->add_used = true;                                      // (from here on the staging and the tables are in use)
-    float* const gain = (float*)((char*)ctx->d_add + n_windows * clx_add::kTableBytes);     // (behind this call's table)
+    clx_call_scratch& s = ctx->add;
+    if (s.begin(ctx, stream, n_windows, (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;
+    void* const d_add = s.d; double* const d_add_part = (double*)s.part.p;
+    clx_add_fill(s.h, n_windows, valid, noise_valid, noise_index, snr_db);
+    HIP_TRY(ctx, hipMemcpyAsync(d_add, s.h, n_windows * clx_add::kTableBytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    float* const gain = (float*)((char*)d_add + n_windows * clx_add::kTableBytes);          // (behind this call's table)
     const float* x = (const float*)d_data;
     if (pl.tc)
         hipLaunchKernelGGL(clx_k_add_sum_tc, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_noise,
-                           (const void*)ctx->d_add, ctx->d_add_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+                           (const void*)d_add, d_add_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
     else
         hipLaunchKernelGGL(clx_k_add_sum, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_noise,
-                           (const void*)ctx->d_add, ctx->d_add_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+                           (const void*)d_add, d_add_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(clx_k_add_gain, dim3(pl.gain_blocks), dim3(clx_add::kThreads), 0, stream, (const void*)ctx->d_add,
-                       (const double*)ctx->d_add_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
+    hipLaunchKernelGGL(clx_k_add_gain, dim3(pl.gain_blocks), dim3(clx_add::kThreads), 0, stream, (const void*)d_add,
+                       (const double*)d_add_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(clx_k_add_apply, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_add::kThreads), 0, stream, (float*)d_data,
-                       (const float*)d_noise, (const void*)ctx->d_add, (const float*)gain, (uint32_t)n_windows, rows, T, pl.tc, pl.n_tiles);
+                       (const float*)d_noise, (const void*)d_add, (const float*)gain, (uint32_t)n_windows, rows, T, pl.tc, pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_add_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -1905,58 +1848,39 @@ extern "C" int clx_reverb_windows(clx_ctx* ctx, const void* d_data, size_t n_win
     if (pl.n_tiles == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_rv_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rv_up, hipEventDisableTiming));
-    if (!ctx->ev_rv_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rv_done, hipEventDisableTiming));
-    const bool grow_tab = n_windows > ctx->rv_cap, grow_part = pl.partials > ctx->rv_part_cap;
-    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
-        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
-        double* d = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc reverb partial sums")) return CLX_API_ERROR;
-        if (ctx->d_rv_part) ctx->rv_old_dev.push_back(ctx->d_rv_part);
-        ctx->d_rv_part = d; ctx->rv_part_cap = want;
-    }
-    if (grow_tab) {
-        const size_t want = n_windows + n_windows / 2 + 64;
-        void* d = nullptr; void* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&d, want * clx_reverb::kTableBytesDevice), "hipMalloc reverb table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc(&h, want * clx_reverb::kTableBytes, hipHostMallocDefault), "hipHostMalloc reverb table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_rv) { ctx->rv_old_dev.push_back(ctx->d_rv); ctx->rv_old_host.push_back(ctx->h_rv); }
-        ctx->d_rv = d; ctx->h_rv = h; ctx->rv_cap = want;
-    }
-    if (ctx->rv_used) {
-        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_rv_up));     // (the upload only: the earlier launch itself is not waited for)
-        if (!grow_tab || !grow_part) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_rv_done, 0));
-    }
-    clx_reverb_fill(ctx->h_rv, n_windows, valid, ir_len, ir_index, opts ? opts->keep_power : 0u);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rv, ctx->h_rv, n_windows * clx_reverb::kTableBytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_rv_up, stream));
-    ctx->rv_used = true;                                       // (from here on the staging and the tables are in use)
-    float* const gain = (float*)((char*)ctx->d_rv + n_windows * clx_reverb::kTableBytes);   // (behind this call's table)
+    clx_call_scratch& s = ctx->rv;
+    // (without keep_power pl.partials is 0: reserved and never replaced, so such a call waits for the last launch even when its table grew)
+    if (s.begin(ctx, stream, n_windows, (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;
+    void* const d_rv = s.d; double* const d_rv_part = (double*)s.part.p;
+    clx_reverb_fill(s.h, n_windows, valid, ir_len, ir_index, opts ? opts->keep_power : 0u);
+    HIP_TRY(ctx, hipMemcpyAsync(d_rv, s.h, n_windows * clx_reverb::kTableBytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    float* const gain = (float*)((char*)d_rv + n_windows * clx_reverb::kTableBytes);        // (behind this call's table)
     const float* x = (const float*)d_data;
     hipLaunchKernelGGL(clx_k_reverb, dim3((unsigned)(n_windows * rows * pl.n_tiles)), dim3(clx_reverb::kThreads), 0, stream, x, (const float*)d_ir,
-                       (const void*)ctx->d_rv, (float*)d_out, (uint32_t)n_windows, rows, T, K, pl.tc, pl.n_tiles);
+                       (const void*)d_rv, (float*)d_out, (uint32_t)n_windows, rows, T, K, pl.tc, pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
     if (pl.power) {                                            // clx_add's sums over (x, y): its table is the head of this one
         if (pl.tc)
             hipLaunchKernelGGL(clx_k_add_sum_tc, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
-                               (const void*)ctx->d_rv, ctx->d_rv_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+                               (const void*)d_rv, d_rv_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
         else
             hipLaunchKernelGGL(clx_k_add_sum, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
-                               (const void*)ctx->d_rv, ctx->d_rv_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+                               (const void*)d_rv, d_rv_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (pl.power || d_gains) {
-        hipLaunchKernelGGL(clx_k_reverb_gain, dim3(pl.gain_blocks), dim3(clx_reverb::kThreads), 0, stream, (const void*)ctx->d_rv,
-                           (const double*)ctx->d_rv_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
+        hipLaunchKernelGGL(clx_k_reverb_gain, dim3(pl.gain_blocks), dim3(clx_reverb::kThreads), 0, stream, (const void*)d_rv,
+                           (const double*)d_rv_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (pl.power) {
         hipLaunchKernelGGL(clx_k_reverb_scale, dim3((unsigned)(n_windows * pl.lines * pl.scale_tiles)), dim3(clx_reverb::kThreads), 0, stream,
-                           (float*)d_out, (const void*)ctx->d_rv, (const float*)gain, (uint32_t)n_windows, pl.lines, pl.line_len, pl.mult,
+                           (float*)d_out, (const void*)d_rv, (const float*)gain, (uint32_t)n_windows, pl.lines, pl.line_len, pl.mult,
                            pl.scale_tiles);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_rv_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -1973,8 +1897,6 @@ extern "C" int clx_reverb_windows_fft(clx_ctx* ctx, const void* d_data, size_t n
     if (!why.empty()) { ctx->last_error = why; return CLX_API_ERROR; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_rvf_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rvf_up, hipEventDisableTiming));
-    if (!ctx->ev_rvf_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rvf_done, hipEventDisableTiming));
     if (!ctx->d_rvf_tw) {                                      // the twiddles, once (the one copy that is waited for)
         std::vector<clx_rvfft::cf> tw(clx_rvfft::kN / 2u);
         clx_rvfft_twiddles(tw.data());
@@ -1984,67 +1906,42 @@ extern "C" int clx_reverb_windows_fft(clx_ctx* ctx, const void* d_data, size_t n
         ctx->d_rvf_tw = d;
     }
     const size_t tab_bytes = fp.table_bytes(n_windows), ws_bytes = (size_t)fp.slots() * clx_rvfft::kSpec * sizeof(clx_rvfft::cf);
-    const bool grow_tab = tab_bytes > ctx->rvf_cap, grow_part = pl.partials > ctx->rvf_part_cap, grow_ws = ws_bytes > ctx->rvf_ws_cap;
-    if (grow_ws) {                                             // larger tables, before anything is queued; the old ones are not freed here
-        const size_t want = ws_bytes + ws_bytes / 2;
-        void* d = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&d, want), "hipMalloc reverb spectra (the workspace of clx_reverb_windows_fft)")) return CLX_API_ERROR;
-        if (ctx->d_rvf_ws) ctx->rvf_old_dev.push_back(ctx->d_rvf_ws);
-        ctx->d_rvf_ws = d; ctx->rvf_ws_cap = want;
-    }
-    if (grow_part) {
-        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
-        double* d = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc reverb partial sums")) return CLX_API_ERROR;
-        if (ctx->d_rvf_part) ctx->rvf_old_dev.push_back(ctx->d_rvf_part);
-        ctx->d_rvf_part = d; ctx->rvf_part_cap = want;
-    }
-    if (grow_tab) {
-        const size_t want = tab_bytes + tab_bytes / 2 + 4096;
-        void* d = nullptr; void* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&d, want), "hipMalloc reverb table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc(&h, want, hipHostMallocDefault), "hipHostMalloc reverb table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_rvf) { ctx->rvf_old_dev.push_back(ctx->d_rvf); ctx->rvf_old_host.push_back(ctx->h_rvf); }
-        ctx->d_rvf = d; ctx->h_rvf = h; ctx->rvf_cap = want;
-    }
-    if (ctx->rvf_used) {
-        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_rvf_up));    // (the upload only: the earlier launch itself is not waited for)
-        if (!grow_tab || !grow_part || !grow_ws) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_rvf_done, 0));
-    }
-    clx_rvfft_fill(ctx->h_rvf, n_windows, valid, ir_len, ir_index, opts ? opts->keep_power : 0u, &fp);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rvf, ctx->h_rvf, tab_bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_rvf_up, stream));
-    ctx->rvf_used = true;                                      // (from here on the staging and the tables are in use)
-    float* const gain = (float*)((char*)ctx->d_rvf + n_windows * clx_reverb::kTableBytes);  // (behind clx_reverb's part of the table)
+    clx_call_scratch& s = ctx->rvf;
+    if (s.begin(ctx, stream, tab_bytes, (size_t)pl.partials, ws_bytes) != CLX_OK) return CLX_API_ERROR;
+    void* const d_rvf = s.d; double* const d_rvf_part = (double*)s.part.p; void* const d_rvf_ws = s.ws.p;
+    clx_rvfft_fill(s.h, n_windows, valid, ir_len, ir_index, opts ? opts->keep_power : 0u, &fp);
+    HIP_TRY(ctx, hipMemcpyAsync(d_rvf, s.h, tab_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    float* const gain = (float*)((char*)d_rvf + n_windows * clx_reverb::kTableBytes);       // (behind clx_reverb's part of the table)
     const float* x = (const float*)d_data;
     const clx_rvfft::cf* tw = (const clx_rvfft::cf*)ctx->d_rvf_tw;
-    hipLaunchKernelGGL(clx_k_rvfft_fwd, dim3((unsigned)fp.slots()), dim3(clx_rvfft::kThreads), 0, stream, x, (const float*)d_ir, (const void*)ctx->d_rvf, tw,
-                       (clx_rvfft::cf*)ctx->d_rvf_ws, (uint32_t)n_windows, rows, T, K, pl.tc, fp.nb, (uint32_t)fp.n_seg);
+    hipLaunchKernelGGL(clx_k_rvfft_fwd, dim3((unsigned)fp.slots()), dim3(clx_rvfft::kThreads), 0, stream, x, (const float*)d_ir, (const void*)d_rvf, tw,
+                       (clx_rvfft::cf*)d_rvf_ws, (uint32_t)n_windows, rows, T, K, pl.tc, fp.nb, (uint32_t)fp.n_seg);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(clx_k_rvfft_mac, dim3((unsigned)fp.n_seg), dim3(clx_rvfft::kThreads), 0, stream, x, (const void*)ctx->d_rvf, tw,
-                       (const clx_rvfft::cf*)ctx->d_rvf_ws, (float*)d_out, (uint32_t)n_windows, rows, T, pl.tc, fp.nb, (uint32_t)fp.n_seg);
+    hipLaunchKernelGGL(clx_k_rvfft_mac, dim3((unsigned)fp.n_seg), dim3(clx_rvfft::kThreads), 0, stream, x, (const void*)d_rvf, tw,
+                       (const clx_rvfft::cf*)d_rvf_ws, (float*)d_out, (uint32_t)n_windows, rows, T, pl.tc, fp.nb, (uint32_t)fp.n_seg);
     HIP_TRY(ctx, hipGetLastError());
     if (pl.power) {                                            // clx_add's sums over (x, y): its table is the head of this one
         if (pl.tc)
             hipLaunchKernelGGL(clx_k_add_sum_tc, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
-                               (const void*)ctx->d_rvf, ctx->d_rvf_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+                               (const void*)d_rvf, d_rvf_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
         else
             hipLaunchKernelGGL(clx_k_add_sum, dim3(pl.sum_blocks), dim3(clx_add::kThreads), 0, stream, x, (const float*)d_out,
-                               (const void*)ctx->d_rvf, ctx->d_rvf_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
+                               (const void*)d_rvf, d_rvf_part, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.units);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (pl.power || d_gains) {
-        hipLaunchKernelGGL(clx_k_reverb_gain, dim3(pl.gain_blocks), dim3(clx_reverb::kThreads), 0, stream, (const void*)ctx->d_rvf,
-                           (const double*)ctx->d_rvf_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
+        hipLaunchKernelGGL(clx_k_reverb_gain, dim3(pl.gain_blocks), dim3(clx_reverb::kThreads), 0, stream, (const void*)d_rvf,
+                           (const double*)d_rvf_part, gain, (float*)d_gains, (uint32_t)n_windows, rows, pl.n_chunks);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (pl.power) {
         hipLaunchKernelGGL(clx_k_reverb_scale, dim3((unsigned)(n_windows * pl.lines * pl.scale_tiles)), dim3(clx_reverb::kThreads), 0, stream,
-                           (float*)d_out, (const void*)ctx->d_rvf, (const float*)gain, (uint32_t)n_windows, pl.lines, pl.line_len, pl.mult,
+                           (float*)d_out, (const void*)d_rvf, (const float*)gain, (uint32_t)n_windows, pl.lines, pl.line_len, pl.mult,
                            pl.scale_tiles);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_rvf_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
@@ -2058,52 +1955,33 @@ extern "C" int clx_specaug_windows(clx_ctx* ctx, const void* d_in, void* d_out, 
     if (pl.n_tiles == 0) return CLX_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    if (!ctx->ev_sa_up) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_sa_up, hipEventDisableTiming));
-    if (!ctx->ev_sa_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_sa_done, hipEventDisableTiming));
     const size_t words = (size_t)pl.table_words, words_dev = words + n_windows;       // (the fills behind this call's table)
-    const bool grow_tab = words_dev > ctx->sa_cap, grow_part = pl.partials > ctx->sa_part_cap;
-    if (grow_part) {                                           // larger tables, before anything is queued; the old ones are not freed here
-        const size_t want = (size_t)pl.partials + (size_t)pl.partials / 2 + 64;
-        double* d = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(double)), "hipMalloc specaug partial sums")) return CLX_API_ERROR;
-        if (ctx->d_sa_part) ctx->sa_old_dev.push_back(ctx->d_sa_part);
-        ctx->d_sa_part = d; ctx->sa_part_cap = want;
-    }
-    if (grow_tab) {
-        const size_t want = words_dev + words_dev / 2 + 64;
-        uint32_t* d = nullptr; uint32_t* h = nullptr;
-        if (!hip_ok(ctx, hipMalloc((void**)&d, want * sizeof(uint32_t)), "hipMalloc specaug table")) return CLX_API_ERROR;
-        if (!hip_ok(ctx, hipHostMalloc((void**)&h, want * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc specaug table")) { (void)hipFree(d); return CLX_API_ERROR; }
-        if (ctx->d_sa) { ctx->sa_old_dev.push_back(ctx->d_sa); ctx->sa_old_host.push_back(ctx->h_sa); }
-        ctx->d_sa = d; ctx->h_sa = h; ctx->sa_cap = want;
-    }
-    if (ctx->sa_used) {
-        if (!grow_tab) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_sa_up));     // (the upload only: the earlier launch itself is not waited for)
-        if (!grow_tab || (!grow_part && pl.mean)) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_sa_done, 0));
-    }
+    clx_call_scratch& s = ctx->sa;
+    // (a constant fill reserves no partial sums, so such a call waits for the last launch only when its table was kept)
+    if (s.begin(ctx, stream, words_dev, pl.mean ? (size_t)pl.partials : clx_call_scratch::kNone) != CLX_OK) return CLX_API_ERROR;
+    uint32_t* const d_sa = (uint32_t*)s.d; double* const d_sa_part = (double*)s.part.p;
     const uint32_t F = fmasks ? opts->n_freq_masks : 0u, M = tmasks ? opts->n_time_masks : 0u;
-    clx_specaug_fill_table(ctx->h_sa, n_windows, rows, valid, warp, fmasks, F, tmasks, M);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sa, ctx->h_sa, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_sa_up, stream));
-    ctx->sa_used = true;                                       // (from here on the staging and the tables are in use)
+    clx_specaug_fill_table((uint32_t*)s.h, n_windows, rows, valid, warp, fmasks, F, tmasks, M);
+    HIP_TRY(ctx, hipMemcpyAsync(d_sa, s.h, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
     if (pl.mean) {
         const float* x = (const float*)d_in;
         if (pl.tc)
-            hipLaunchKernelGGL(clx_k_norm_sum_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_sa,
-                               ctx->d_sa_part, rows, T, pl.n_chunks, pl.n_groups);
+            hipLaunchKernelGGL(clx_k_norm_sum_tc, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)d_sa,
+                               d_sa_part, rows, T, pl.n_chunks, pl.n_groups);
         else
-            hipLaunchKernelGGL(clx_k_norm_sum, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)ctx->d_sa,
-                               ctx->d_sa_part, rows, T, pl.n_chunks, (uint64_t)n_windows * rows * pl.n_chunks);
+            hipLaunchKernelGGL(clx_k_norm_sum, dim3(pl.sum_blocks), dim3(clx_norm::kThreads), 0, stream, x, (const uint32_t*)d_sa,
+                               d_sa_part, rows, T, pl.n_chunks, (uint64_t)n_windows * rows * pl.n_chunks);
         HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(clx_k_specaug_fill, dim3(pl.fill_blocks), dim3(clx_specaug::kThreads), 0, stream, (const uint32_t*)ctx->d_sa,
-                           (const double*)ctx->d_sa_part, (float*)(ctx->d_sa + words), (uint32_t)n_windows, rows, pl.n_chunks);
+        hipLaunchKernelGGL(clx_k_specaug_fill, dim3(pl.fill_blocks), dim3(clx_specaug::kThreads), 0, stream, (const uint32_t*)d_sa,
+                           (const double*)d_sa_part, (float*)(d_sa + words), (uint32_t)n_windows, rows, pl.n_chunks);
         HIP_TRY(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(clx_k_specaug, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_specaug::kThreads), 0, stream, (const uint32_t*)d_in,
-                       (uint32_t*)d_out, (const uint32_t*)ctx->d_sa, (float*)d_fill, (uint32_t)n_windows, rows, T, F, M, pl.mean,
+                       (uint32_t*)d_out, (const uint32_t*)d_sa, (float*)d_fill, (uint32_t)n_windows, rows, T, F, M, pl.mean,
                        opts->fill_mean ? 0.f : opts->fill, pl.tc, pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_sa_done, stream));
+    HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
 }
 
