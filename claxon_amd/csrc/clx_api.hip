@@ -256,9 +256,12 @@ static_assert(CLX_SUBMIT_MERGE <= CLX_MAX_MERGE && CLX_SUBMIT_STREAMS * CLX_SUBM
 //    rewrites the staging.  A call that replaced the table has a staging nobody reads and does not wait;
 //  - ev_done is behind the last launch: the call's stream (not the host) waits for it before anything rewrites what that launch
 //    may read.  Only a call that replaced EVERY buffer it reserved goes without; a reserved buffer that did not grow counts as
-//    kept, one reserved with need 0 included.  Two asymmetries follow, and both are as they have always been:
-//    clx_reverb_windows without keep_power reserves 0 partial sums and so always waits, even when its table grew;
-//    clx_specaug_windows with a constant fill reserves no partial sums at all and so waits only when its table was kept.
+//    kept, one reserved with need 0 included.  That is sound only if a call reserves every device-only buffer its set has,
+//    with need 0 where it has no use for one: the next call waits for this call's launch alone, so this call has to stand
+//    behind every earlier launch on a buffer the next one may meet.  Hence clx_reverb_windows without keep_power and
+//    clx_specaug_windows with a constant fill reserve 0 partial sums, and wait once their set is in use even when their
+//    table grew.  (The latter used to reserve none and to wait only when its table was kept: a mean-fill call on another
+//    stream behind it then waited for it alone and wrote the sums an earlier mean-fill call's kernels were still using.)
 // An entry point calls begin() before it fills the staging, uploaded() behind its hipMemcpyAsync of the table and done() behind
 // its last launch; clx_destroy calls release().  Needs and capacities of the table are counted in the set's own unit (windows,
 // 32-bit words or bytes).
@@ -1957,8 +1960,10 @@ extern "C" int clx_specaug_windows(clx_ctx* ctx, const void* d_in, void* d_out, 
     hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
     const size_t words = (size_t)pl.table_words, words_dev = words + n_windows;       // (the fills behind this call's table)
     clx_call_scratch& s = ctx->sa;
-    // (a constant fill reserves no partial sums, so such a call waits for the last launch only when its table was kept)
-    if (s.begin(ctx, stream, words_dev, pl.mean ? (size_t)pl.partials : clx_call_scratch::kNone) != CLX_OK) return CLX_API_ERROR;
+    // (with a constant fill pl.partials is 0: reserved and never replaced, so such a call waits for the last launch even when its
+    // table grew.  It has no use for the sums, but the next mean-fill call waits for this launch alone and must find it behind the
+    // last one that used them)
+    if (s.begin(ctx, stream, words_dev, (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;
     uint32_t* const d_sa = (uint32_t*)s.d; double* const d_sa_part = (double*)s.part.p;
     const uint32_t F = fmasks ? opts->n_freq_masks : 0u, M = tmasks ? opts->n_time_masks : 0u;
     clx_specaug_fill_table((uint32_t*)s.h, n_windows, rows, valid, warp, fmasks, F, tmasks, M);
