@@ -103,12 +103,13 @@ EXPORTS = [
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
     "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
+    "clx_splice_windows", "clx_splice_deltas",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -200,6 +201,8 @@ def lib():
     L.clx_reverb_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_reverb_windows_fft.argtypes = L.clx_reverb_windows.argtypes
     L.clx_specaug_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.clx_splice_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
+    L.clx_splice_deltas.argtypes = [C.c_uint32, C.c_uint32, vp, vp, u32p]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -947,6 +950,50 @@ class Context:
                                               None if warp is None else _np_ptr(warp), None if fm is None else _np_ptr(fm),
                                               None if tm is None else _np_ptr(tm), C.byref(opts), f_ptr,
                                               C.c_void_p(handle) if handle else None))
+        return out
+
+    def splice_windows(self, data, valid, layout, splice, out=None, stream=None):
+        """clx_splice_windows: the dense float32 feature batch `data` -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows
+        1..256 -- spliced by `splice` (a Splice: deltas, context frames, subsampling, low-frame-rate stacking), out of place: window
+        k's first valid[k] frames give its first splice.frames_out(valid[k]) output frames of splice.n_out(rows) rows, every tap
+        clamped into [0, valid[k]) (the edge frame repeated; claxon_hip.h has the definition and the order of the taps); the
+        output frames from there on are splice.pad.  `out` is [B, splice.n_out(rows), splice.frames_out(T)] (CT) or the same
+        transposed (TC) and must not be data (None: a new tensor).  `data` and `out` are CUDA float32 tensors, or `data` is a
+        (pointer, B, rows, T) tuple and `out` a pointer.  `data` is not written, and nothing of it from valid[k] on is read.
+        Asynchronous on `stream` as gather_windows is.  Returns `out`.  read_mel(..., splice=) runs this before normalize=; whoever
+        wants CMVN in front of the deltas calls norm_windows and then this."""
+        if not isinstance(splice, Splice):
+            raise ValueError("splice_windows: splice must be a Splice, not %r" % (splice,))
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("splice_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("splice_windows: %s is out of range" % name)
+        shape = (B, splice.frames_out(T), splice.n_out(rows)) if tc else (B, splice.n_out(rows), splice.frames_out(T))
+        if hasattr(data, "data_ptr") and out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        if hasattr(out, "data_ptr"):
+            if not hasattr(data, "data_ptr") or tuple(out.shape) != shape or not out.is_contiguous() or str(out.dtype) != "torch.float32":
+                raise ValueError("splice_windows: out must be a contiguous float32 tensor of shape %r" % (shape,))
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("splice_windows: valid has %d entries for %d windows" % (valid.size, B))
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
+        blocks, coefs = splice._tables()
+        opts = _SpliceOpts(len(splice.blocks), splice.stride, splice.pad, 0)
+        self._check(lib().clx_splice_windows(self._h, d_ptr, o_ptr, B, rows, T, _np_ptr(valid), int(layout), _np_ptr(blocks),
+                                             _np_ptr(coefs) if coefs.size else None, C.byref(opts), C.c_void_p(handle) if handle else None))
         return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -1973,6 +2020,124 @@ class Norm:
         return hash((self.mean, self.var, self.ddof, self.eps, self.pad))
 
 
+# ---- frame splicing: deltas, context, subsampling, low frame rate ------------------------------------------------------------------
+
+SPLICE_MAX_BLOCKS, SPLICE_MAX_STRIDE, SPLICE_MAX_OFFSET, SPLICE_MAX_HALF, SPLICE_MAX_OUT_ROWS = 32, 64, 64, 16, 8192
+
+
+class _SpliceOpts(C.Structure):          # clx_splice_opts
+    _fields_ = [("n_blocks", C.c_uint32), ("stride", C.c_uint32), ("pad", C.c_float), ("reserved", C.c_uint32)]
+
+
+def _splice_whole(v, lo, hi, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError("Splice: %s must be a whole number in %d..%d, not %r" % (what, lo, hi, v))
+    return int(v)
+
+
+class Splice:
+    """What Context.splice_windows and read_mel(..., splice=) do along time to every row of every window (clx_splice_windows,
+    claxon_hip.h): `blocks` is a list of (offset, coefs): coefs None is a copy block, output frame u of it is input frame
+    u * stride + offset; otherwise an odd number 2m + 1 <= 33 of finite coefficients c[-m .. m], and the frame is the sum over d
+    of c[d] times input frame u * stride + offset + d, added up by fused multiply-adds in ascending d.  Every frame index is
+    clamped into the window's valid frames, so the first and the last frame repeat.  The K <= 32 blocks stand one behind the other
+    in the output's rows: n_out(rows) = K * rows (8192 at most); an input of n frames gives frames_out(n) = ceil(n / stride);
+    output frames behind a window's own are `pad`.  A plain value: it owns nothing on the device.  deltas(), context(),
+    subsample() and lfr() build the plans of Kaldi's add-deltas, splice-feats and subsample-feats and of FunASR's apply_lfr, as this
+    project reads them.  ValueError for what the ranges above exclude."""
+
+    def __init__(self, blocks, stride=1, pad=0.0):
+        self.stride = _splice_whole(stride, 1, SPLICE_MAX_STRIDE, "stride")
+        if isinstance(pad, bool) or not isinstance(pad, (int, float, np.integer, np.floating)) or not math.isfinite(float(pad)) \
+                or abs(float(pad)) > float(np.finfo(np.float32).max):
+            raise ValueError("Splice: pad must be a finite number, not %r" % (pad,))
+        self.pad = float(np.float32(pad))
+        try:
+            blocks = [tuple(b) for b in blocks]
+        except TypeError:
+            blocks = None
+        if not blocks or len(blocks) > SPLICE_MAX_BLOCKS or any(len(b) != 2 for b in blocks):
+            raise ValueError("Splice: blocks must be a list of 1..%d (offset, coefs or None) pairs" % SPLICE_MAX_BLOCKS)
+        out = []
+        for off, coefs in blocks:
+            off = _splice_whole(off, -SPLICE_MAX_OFFSET, SPLICE_MAX_OFFSET, "an offset")
+            if coefs is not None:
+                c = np.asarray(coefs)
+                if c.ndim != 1 or c.size % 2 != 1 or c.size > 2 * SPLICE_MAX_HALF + 1 or c.dtype.kind not in "fiu":
+                    raise ValueError("Splice: a block's coefs must be None or an odd number, at most %d, of numbers" % (2 * SPLICE_MAX_HALF + 1))
+                with np.errstate(over="ignore"):
+                    c = c.astype(np.float64).astype(np.float32)              # (one rounding of what the caller gave)
+                if not np.all(np.isfinite(c)):
+                    raise ValueError("Splice: a block's coefs must be finite float32 values")
+                coefs = tuple(float(v) for v in c)
+            out.append((off, coefs))
+        self.blocks = tuple(out)
+
+    @classmethod
+    def deltas(cls, order=2, window=2, pad=0.0):
+        """Kaldi's add-deltas (DeltaFeatures): the features, then their order-i deltas for i = 1 .. order, each the i-fold
+        convolution of [-window .. window] / (2 * sum d^2) with itself over the edge-repeated frames -- one combined filter of
+        2 * i * window + 1 taps, clamped once; applying the first-order filter i times is not the same in the edge frames.
+        order 0..4 and order * window at most 16.  The coefficients come from clx_splice_deltas: exact whole numerators and
+        denominators, divided in double, rounded once to float32."""
+        order = _splice_whole(order, 0, 4, "order")
+        window = _splice_whole(window, 1 if order else 0, SPLICE_MAX_HALF // order if order else 1 << 30, "window (order * window at most 16)")
+        blk = np.zeros((order + 1, 4), dtype=np.int32)
+        coefs = np.zeros(max(1, order * (order * window + window + 1)), dtype=np.float32)
+        n = C.c_uint32(0)
+        if lib().clx_splice_deltas(order, window, _np_ptr(blk), _np_ptr(coefs), C.byref(n)) != OK:
+            raise ValueError("Splice.deltas: order %r and window %r are refused" % (order, window))
+        return cls([(0, None)] + [(0, coefs[int(b[3]):int(b[3]) + 2 * int(b[1]) + 1]) for b in blk[1:]], 1, pad)
+
+    @classmethod
+    def context(cls, left, right, pad=0.0):
+        """Kaldi's splice-feats: left + right + 1 copy blocks, the frames at offsets -left .. right."""
+        left, right = _splice_whole(left, 0, SPLICE_MAX_OFFSET, "left"), _splice_whole(right, 0, SPLICE_MAX_OFFSET, "right")
+        if left + right + 1 > SPLICE_MAX_BLOCKS:
+            raise ValueError("Splice: left + right + 1 must be at most %d blocks, not %d" % (SPLICE_MAX_BLOCKS, left + right + 1))
+        return cls([(o, None) for o in range(-left, right + 1)], 1, pad)
+
+    @classmethod
+    def subsample(cls, n, pad=0.0):
+        """Kaldi's subsample-feats: every n-th frame, from frame 0."""
+        return cls([(0, None)], _splice_whole(n, 1, SPLICE_MAX_STRIDE, "n"), pad)
+
+    @classmethod
+    def lfr(cls, m=7, n=6, pad=0.0):
+        """FunASR's apply_lfr (Paraformer, SenseVoice): m frames stacked at a stride of n, the first frame repeated (m - 1) // 2 times
+        in front and the last frame repeated behind: m copy blocks at offsets -((m - 1) // 2) .. m - 1 - (m - 1) // 2."""
+        m, n = _splice_whole(m, 1, SPLICE_MAX_BLOCKS, "m"), _splice_whole(n, 1, SPLICE_MAX_STRIDE, "n")
+        return cls([(o - (m - 1) // 2, None) for o in range(m)], n, pad)
+
+    def n_out(self, rows):
+        """Output rows for `rows` input rows."""
+        return len(self.blocks) * int(rows)
+
+    def frames_out(self, n):
+        """Output frames for n input frames (a number or an array of them): ceil(n / stride)."""
+        if isinstance(n, np.ndarray):
+            return (n + (self.stride - 1)) // self.stride
+        return (int(n) + self.stride - 1) // self.stride
+
+    def _tables(self):
+        """(blocks [K, 4] int32: offset, m, copy, first coefficient; coefs float32) for clx_splice_windows."""
+        blk = np.zeros((len(self.blocks), 4), dtype=np.int32)
+        coefs = []
+        for j, (off, c) in enumerate(self.blocks):
+            blk[j] = (off, 0, 1, 0) if c is None else (off, len(c) // 2, 0, len(coefs))
+            coefs.extend(c or ())
+        return blk, np.array(coefs, dtype=np.float32)
+
+    def __repr__(self):
+        return "Splice(%r, stride=%d, pad=%r)" % ([(o, None if c is None else list(c)) for o, c in self.blocks], self.stride, self.pad)
+
+    def __eq__(self, other):
+        return isinstance(other, Splice) and (self.blocks, self.stride, self.pad) == (other.blocks, other.stride, other.pad)
+
+    def __hash__(self):
+        return hash((self.blocks, self.stride, self.pad))
+
+
 # ---- SpecAugment ----------------------------------------------------------------------------------------------------------------
 
 SPECAUG_MAX_MASKS = 32
@@ -2568,7 +2733,7 @@ class StreamSet:
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -2605,11 +2770,23 @@ class StreamSet:
         place: the tensor returned is a second one, and the one it was made from is released when the call returns, like read()'s
         scratch.  As with every launch here, on torch's default stream the work goes to the context's own stream, which torch's
         stream is not ordered against: wait (torch.cuda.synchronize()) before the next torch operation on the device.
-        valid_frames does not change, and the frames behind them keep what they held.  augment=None is the call without the argument."""
+        valid_frames does not change, and the frames behind them keep what they held.  augment=None is the call without the argument.
+
+        With splice=Splice(...) the features are spliced along time (Kaldi's add-deltas, splice-feats and subsample-feats, FunASR's
+        low-frame-rate stacking): one clx_splice_windows call behind the spec's own launches, a ranged spec's range step included,
+        and in front of normalize= and augment=, which then see splice.n_out(n_out) rows, splice.frames_out(n_frames) frames and
+        valid_frames' = splice.frames_out(valid_frames) -- FunASR's order: stacking, then CMVN, then masking.  The tensor returned
+        is [B, splice.n_out(n_out), splice.frames_out(n_frames)] ("ct") or the same transposed ("tc"), with valid_frames'; the
+        frames behind them are splice.pad unless a later step says otherwise.  A later step that refuses the row count (normalize=
+        and augment= take 256 rows at most, so not the 560 of seven stacked 80-band frames) raises its own error.  The step is
+        out of place and the tensor it was made from is released on return, like read()'s scratch.  Whoever wants CMVN in front of
+        the deltas calls read_mel(normalize=) and then Context.splice_windows.  splice=None is the call without the argument."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
         if augment is not None and not isinstance(augment, (SpecAugment, SpecAugmentPlan)):
             raise ValueError("read_mel: augment must be a SpecAugment, a SpecAugmentPlan or None, not %r" % (augment,))
+        if splice is not None and not isinstance(splice, Splice):
+            raise ValueError("read_mel: splice must be a Splice or None, not %r" % (splice,))
         if add is not None and not isinstance(add, Add):
             raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
         if reverb is not None and not isinstance(reverb, Reverb):
@@ -2642,11 +2819,15 @@ class StreamSet:
         valid = valid.numpy()
         self.ctx.mel_windows(spec, audio.view(B, L), valid, n_frames, _LAYOUTS[layout], out)
         vf = spec.valid_frames(valid, n_frames)
+        rows = spec.n_out
+        if splice is not None:
+            out = self.ctx.splice_windows(out, vf, _LAYOUTS[layout], splice)
+            rows, n_frames, vf = splice.n_out(rows), splice.frames_out(n_frames), splice.frames_out(vf)
         if normalize is not None:
             self.ctx.norm_windows(out, vf, _LAYOUTS[layout], normalize)
         if augment is not None:
-            plan = augment.draw(vf, spec.n_out) if isinstance(augment, SpecAugment) else augment
-            _specaug_fit(plan, vf, spec.n_out, n_frames, "read_mel")
+            plan = augment.draw(vf, rows) if isinstance(augment, SpecAugment) else augment
+            _specaug_fit(plan, vf, rows, n_frames, "read_mel")
             if B and n_frames:
                 out = self.ctx.specaug_windows(out, vf, _LAYOUTS[layout], plan.warp, plan.freq_masks, plan.time_masks, plan.fill)
         return out, torch.from_numpy(vf)

@@ -18,6 +18,7 @@
 #include "clx_reverb.hip"
 #include "clx_reverb_fft.hip"
 #include "clx_specaug.hip"
+#include "clx_splice.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -334,6 +335,8 @@ struct clx_ctx {
     // clx_specaug_windows (in 32-bit words: the masks of a call are as many as it says): V, the warp pairs and the clipped masks
     // per window; behind them on the device the fills
     clx_call_scratch sa { "specaug", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    // clx_splice_windows (in 32-bit words): V per window, the plan's blocks and their coefficients
+    clx_call_scratch sp { "splice", 64, sizeof(uint32_t), sizeof(uint32_t) };
 };
 
 struct clx_mel_spec {
@@ -549,6 +552,7 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->rvf.old_dev.push_back(ctx->d_rvf_tw);                 // (the same)
     ctx->rvf.release();
     ctx->sa.release();
+    ctx->sp.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1988,6 +1992,35 @@ extern "C" int clx_specaug_windows(clx_ctx* ctx, const void* d_in, void* d_out, 
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, s.done(stream));
     return CLX_OK;
+}
+
+extern "C" int clx_splice_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                  uint32_t layout, const clx_splice_block* blocks, const float* coefs, const clx_splice_opts* opts, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_splice_plan pl;
+    const char* why = clx_splice_check(d_in, d_out, n_windows, rows, T, valid, layout, blocks, coefs, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    const size_t words = (size_t)pl.table_words;
+    clx_call_scratch& s = ctx->sp;
+    if (s.begin(ctx, stream, words) != CLX_OK) return CLX_API_ERROR;       // (the set has no device-only buffer)
+    clx_splice_fill_table((uint32_t*)s.h, n_windows, valid, blocks, coefs, opts->n_blocks);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    uint32_t pad;
+    memcpy(&pad, &opts->pad, sizeof pad);
+    hipLaunchKernelGGL(clx_k_splice, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_splice::kThreads), 0, stream, (const uint32_t*)d_in,
+                       (uint32_t*)d_out, (const uint32_t*)s.d, (uint32_t)n_windows, rows, T, pl.T_out, opts->n_blocks, opts->stride, pl.H,
+                       pl.n_coefs, pad, pl.tc, pl.n_tiles, pl.Fs, pl.Rc);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_splice_deltas(uint32_t order, uint32_t window, clx_splice_block* blocks, float* coefs, uint32_t* n_coefs) {
+    return clx_splice_deltas_build(order, window, blocks, coefs, n_coefs) ? CLX_API_ERROR : CLX_OK;
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

@@ -857,6 +857,43 @@ typedef struct { uint32_t n_freq_masks, n_time_masks, fill_mean; float fill; uin
 int  clx_specaug_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
                          uint32_t layout, const uint32_t* warp, const uint32_t* fmasks, const uint32_t* tmasks,
                          const clx_specaug_opts* opts, void* d_fill, void* stream);
+/* Frame splicing of a dense float32 feature batch on the device, out of place: blocks of small time-domain FIRs over every window's
+ * valid frames, the edge frame repeated, with an output stride.  Kaldi's add-deltas, splice-feats and subsample-feats and FunASR's
+ * low-frame-rate stacking are plans of it (claxon_amd.Splice builds them).  d_in is [n_windows][rows][T] (CLX_WINDOW_CT) or
+ * [n_windows][T][rows] (CLX_WINDOW_TC), rows in 1..256, and is never written.  Window k has V = valid[k] <= T live frames.
+ *
+ *   plan       K = opts->n_blocks blocks (1..32), a stride s = opts->stride (1..64); block j is blocks[j]: an offset o_j
+ *              (|o_j| <= 64), a half-width m_j (0..16) and either copy = 1 (then m_j = 0) or copy = 0 and the 2 m_j + 1 float32
+ *              coefficients c_j[-m_j .. m_j] at coefs[coef .. coef + 2 m_j].  K * rows is at most 8192.
+ *   output     d_out is [n_windows][K * rows][T_out] (CT) or [n_windows][T_out][K * rows] (TC), T_out = ceil(T / s); the call
+ *              writes every float of it.  Window k has V_out = ceil(V / s) live output frames.
+ *   live       for u < V_out, with t = u s + o_j and clamp(i) = min(max(i, 0), V - 1), row j * rows + r of frame u is
+ *                copy block   the 32-bit word of x[r][clamp(t)], moved and never interpreted: NaN payloads and -0.0 survive;
+ *                FIR block    acc after acc = +0.0f; acc = fmaf(c_j[d], x[r][clamp(t + d)], acc) for d = -m_j .. m_j ascending:
+ *                             2 m_j + 1 fused steps, one rounding each; no tap is skipped, a zero coefficient included.
+ *   padding    a frame u >= V_out is the word of opts->pad in every row; a window with V = 0 is all padding.
+ *   reads      no cell of d_in outside the frames [0, V) of its window is read, whatever it holds.
+ *   layouts    CT and TC of the same data give the same words.
+ *
+ * valid, blocks and coefs are host arrays, staged as clx_specaug_windows stages its arrays (one pinned table a call, tables that
+ * have to grow replaced before anything is queued, one event behind the upload and one behind the launch), so the call is
+ * asynchronous on `stream` (NULL: the context's), returns without waiting for the device and the arrays may be reused at once.
+ * CLX_API_ERROR, each with a clx_last_error text of its own, for opts == NULL, reserved bits, n_blocks outside 1..32, a stride
+ * outside 1..64, an unknown layout, rows outside 1..256 (so K * rows cannot pass 8192), T above 2^31 - 1, blocks == NULL, an offset, a
+ * half-width or a copy mark out of range, a copy block with a half-width, a FIR block with coefs == NULL, a null d_in, d_out or
+ * valid, d_out == d_in and a valid[k] > T.  n_windows == 0 or T == 0 succeeds and launches nothing.  Not here: per-window plans,
+ * running in place, deltas in frequency.
+ *
+ * clx_splice_deltas fills the plan of Kaldi's DeltaFeatures (host only, no context): block 0 a copy, block i = 1 .. order the
+ * i-fold convolution of [-window .. window] / (2 sum_{d = 1 .. window} d^2) with itself at offset 0, m_i = i * window, the clamp
+ * applied once to the combined filter.  The numerators and the denominators (2 sum d^2)^i are whole numbers; a coefficient is
+ * (float)((double)num / (double)den).  blocks receives order + 1 entries, coefs their coefficients (84 floats at most), *n_coefs
+ * their count.  CLX_API_ERROR for a null argument, order above 4, and with order >= 1 a window of 0 or order * window above 16. */
+typedef struct { int32_t offset; uint32_t m, copy, coef; } clx_splice_block;
+typedef struct { uint32_t n_blocks, stride; float pad; uint32_t reserved; } clx_splice_opts;
+int  clx_splice_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                        uint32_t layout, const clx_splice_block* blocks, const float* coefs, const clx_splice_opts* opts, void* stream);
+int  clx_splice_deltas(uint32_t order, uint32_t window, clx_splice_block* blocks, float* coefs, uint32_t* n_coefs);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
