@@ -103,13 +103,13 @@ EXPORTS = [
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
     "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
-    "clx_splice_windows", "clx_splice_deltas",
+    "clx_splice_windows", "clx_splice_deltas", "clx_cmvn_global_windows", "clx_cmvn_sliding_windows", "clx_cmvn_from_stats",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -203,6 +203,9 @@ def lib():
     L.clx_specaug_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.clx_splice_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_splice_deltas.argtypes = [C.c_uint32, C.c_uint32, vp, vp, u32p]
+    L.clx_cmvn_global_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
+    L.clx_cmvn_sliding_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]
+    L.clx_cmvn_from_stats.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -994,6 +997,56 @@ class Context:
         opts = _SpliceOpts(len(splice.blocks), splice.stride, splice.pad, 0)
         self._check(lib().clx_splice_windows(self._h, d_ptr, o_ptr, B, rows, T, _np_ptr(valid), int(layout), _np_ptr(blocks),
                                              _np_ptr(coefs) if coefs.size else None, C.byref(opts), C.c_void_p(handle) if handle else None))
+        return out
+
+    def cmvn_windows(self, data, valid, layout, cmvn, out=None, stream=None):
+        """clx_cmvn_global_windows or clx_cmvn_sliding_windows, as `cmvn` (a Cmvn) says, over the dense float32 feature batch `data`
+        -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows 1..8192 -- and the first valid[k] frames of window k
+        (claxon_hip.h has the definitions, the statistics window and the order of the sums); every frame from valid[k] on becomes
+        cmvn.pad.  A global Cmvn (cmvn.rows == rows) works in place: `out` must be None, and `data` is returned.  A sliding one is
+        out of place: `out` has data's shape and must not be data (None: a new tensor), `data` is not written and nothing of it
+        from valid[k] on is read; `out` is returned.  `data` and `out` are CUDA float32 tensors, or `data` is a (pointer, B, rows, T)
+        tuple and `out` a pointer.  Asynchronous on `stream` as gather_windows is."""
+        if not isinstance(cmvn, Cmvn):
+            raise ValueError("cmvn_windows: cmvn must be a Cmvn, not %r" % (cmvn,))
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("cmvn_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("cmvn_windows: %s is out of range" % name)
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("cmvn_windows: valid has %d entries for %d windows" % (valid.size, B))
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        handle = C.c_void_p(handle) if handle else None
+        if cmvn.rows is not None:
+            if out is not None:
+                raise ValueError("cmvn_windows: a global Cmvn works in place: out must be None")
+            if cmvn.rows != rows:
+                raise ValueError("cmvn_windows: the Cmvn has %d rows, the batch %d" % (cmvn.rows, rows))
+            opts = _CmvnGlobalOpts(cmvn.pad, 0)
+            self._check(lib().clx_cmvn_global_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), int(layout), _np_ptr(cmvn._shift),
+                                                      _np_ptr(cmvn._scale), C.byref(opts), handle))
+            return data
+        shape = (B, T, rows) if tc else (B, rows, T)
+        if hasattr(data, "data_ptr") and out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        if hasattr(out, "data_ptr"):
+            if not hasattr(data, "data_ptr") or tuple(out.shape) != shape or not out.is_contiguous() or str(out.dtype) != "torch.float32":
+                raise ValueError("cmvn_windows: out must be a contiguous float32 tensor of shape %r" % (shape,))
+        o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
+        opts = cmvn._sliding_opts()
+        self._check(lib().clx_cmvn_sliding_windows(self._h, d_ptr, o_ptr, B, rows, T, _np_ptr(valid), int(layout), C.byref(opts), handle))
         return out
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
@@ -2138,6 +2191,171 @@ class Splice:
         return hash((self.blocks, self.stride, self.pad))
 
 
+# ---- global and sliding-window CMVN --------------------------------------------------------------------------------------------
+
+CMVN_MAX_ROWS, CMVN_MAX_WINDOW = 8192, 1024
+
+
+class _CmvnGlobalOpts(C.Structure):      # clx_cmvn_global_opts
+    _fields_ = [("pad", C.c_float), ("reserved", C.c_uint32)]
+
+
+class _CmvnSlidingOpts(C.Structure):     # clx_cmvn_sliding_opts
+    _fields_ = [("window", C.c_uint32), ("min_window", C.c_uint32), ("center", C.c_uint32), ("norm_vars", C.c_uint32), ("pad", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
+def _cmvn_pad(pad):
+    if isinstance(pad, bool) or not isinstance(pad, (int, float, np.integer, np.floating)) or not math.isfinite(float(pad)) \
+            or abs(float(pad)) > float(np.finfo(np.float32).max):
+        raise ValueError("Cmvn: pad must be a finite number, not %r" % (pad,))
+    return float(np.float32(pad))
+
+
+def _cmvn_row(v, what, n=None):
+    """`v` as a float64 vector of 1..8192 finite numbers (n: of exactly n)."""
+    try:
+        a = np.asarray(v)
+    except Exception:
+        a = None
+    if a is None or a.ndim != 1 or a.dtype.kind not in "fiu" or not 1 <= a.size <= CMVN_MAX_ROWS or (n is not None and a.size != n):
+        raise ValueError("Cmvn: %s must be a vector of %s numbers" % (what, "1..%d" % CMVN_MAX_ROWS if n is None else "%d" % n))
+    a = a.astype(np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("Cmvn: %s must be finite" % what)
+    return a
+
+
+def _cmvn_f32(a, what):
+    with np.errstate(over="ignore"):
+        f = a.astype(np.float32)                             # (one rounding of what the caller gave)
+    if not np.all(np.isfinite(f)):
+        raise ValueError("Cmvn: %s must be finite float32 values" % what)
+    return np.ascontiguousarray(f)
+
+
+def _cmvn_whole(v, lo, hi, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError("Cmvn: %s must be a whole number in %d..%d, not %r" % (what, lo, hi, v))
+    return int(v)
+
+
+def _cmvn_flag(v, what):
+    if not isinstance(v, (bool, int, np.integer, np.bool_)) or int(v) not in (0, 1):
+        raise ValueError("Cmvn: %s must be 0 or 1, not %r" % (what, v))
+    return bool(v)
+
+
+class Cmvn:
+    """What Context.cmvn_windows and read_mel(..., cmvn=) do to every window: cepstral mean and variance normalisation whose
+    statistics are not the window's own (that one is Norm).  A plain value: it owns nothing on the device.  Two kinds:
+
+    global     a fixed float32 shift and scale per row: y = (x + shift[r]) * scale[r], two float32 operations, bit for bit what
+               numpy or torch give for that expression (clx_cmvn_global_windows; in place).  global_(shift, scale),
+               from_mean_std(mean, std) (WeNet's (x - mean) * istd: shift = -mean, scale = float32(1 / float64(std)); ESPnet's
+               GlobalMVN divides by std instead, which is not bit-equal) and from_kaldi_stats(stats) (a Kaldi CMVN accumulator,
+               [2][rows + 1]: clx_cmvn_from_stats) build one; FunASR's am.mvn is global_(means, vars).  .rows is the row count.
+    sliding    the mean (and with norm_vars the standard deviation) of each row over a window of frames around (center) or up to
+               (not center) the cell's own frame: Kaldi's apply-cmvn-sliding as this project reads it (clx_cmvn_sliding_windows; out
+               of place).  sliding(window, min_window, center, norm_vars) builds one, xvector() is the x-vector recipes'
+               sliding(300, 100, True, False).  .rows is None.
+
+    Frames behind a window's valid ones become `pad`.  ValueError for a shift or scale that is not 1..8192 finite float32 numbers,
+    for vectors of different lengths, a std that is not above 0, a stats matrix that is not [2][rows + 1] or whose count is not
+    above 0, a window outside 1..1024, a min_window outside 1..window, a flag that is not 0 / 1 and a pad that is not finite."""
+
+    def __init__(self, shift=None, scale=None, window=None, min_window=None, center=False, norm_vars=False, pad=0.0):
+        self.pad = _cmvn_pad(pad)
+        if (shift is None) != (scale is None) or (shift is None) == (window is None):
+            raise ValueError("Cmvn: give shift and scale (a global one) or window (a sliding one); see global_() and sliding()")
+        if shift is not None:
+            self._shift = _cmvn_f32(_cmvn_row(shift, "shift"), "shift")
+            self._scale = _cmvn_f32(_cmvn_row(scale, "scale", self._shift.size), "scale")
+            self.rows = int(self._shift.size)
+            self.window = self.min_window = None
+            self.center = self.norm_vars = False
+        else:
+            self._shift = self._scale = None
+            self.rows = None
+            self.window = _cmvn_whole(window, 1, CMVN_MAX_WINDOW, "window")
+            self.center, self.norm_vars = _cmvn_flag(center, "center"), _cmvn_flag(norm_vars, "norm_vars")
+            self.min_window = _cmvn_whole(self.window if min_window is None else min_window, 1, self.window, "min_window (at most window)")
+
+    @classmethod
+    def global_(cls, shift, scale, pad=0.0):
+        """y = (x + shift[r]) * scale[r] in float32: FunASR's am.mvn is global_(means, vars) behind Splice.lfr()."""
+        return cls(shift=shift, scale=scale, pad=pad)
+
+    @classmethod
+    def from_mean_std(cls, mean, std, pad=0.0):
+        """(x - mean) * (1 / std): shift = float32(-mean), scale = float32(1 / float64(std)); WeNet's global_cmvn with istd = 1 / std."""
+        mean = _cmvn_row(mean, "mean")
+        std = _cmvn_row(std, "std", mean.size)
+        if not np.all(std > 0):
+            raise ValueError("Cmvn: std must be above 0")
+        return cls(shift=-mean, scale=1.0 / std, pad=pad)
+
+    @classmethod
+    def from_kaldi_stats(cls, stats, norm_vars=True, pad=0.0):
+        """From a Kaldi CMVN accumulator (compute-cmvn-stats): [2][rows + 1], the sums and the count in row 0, the sums of squares
+        in row 1.  clx_cmvn_from_stats: mean = sum / count, var = max(sumsq / count - mean^2, 1e-20), shift = -mean,
+        scale = 1 / sqrt(var) (1 without norm_vars), in double, rounded once.  Kaldi's apply-cmvn computes x * scale + offset, a
+        different rounding of the same value."""
+        norm_vars = _cmvn_flag(norm_vars, "norm_vars")
+        try:
+            st = np.asarray(stats)
+        except Exception:
+            st = None
+        if st is None or st.ndim != 2 or st.shape[0] != 2 or not 2 <= st.shape[1] <= CMVN_MAX_ROWS + 1 or st.dtype.kind not in "fiu":
+            raise ValueError("Cmvn: stats must be a [2][rows + 1] matrix of numbers, rows in 1..%d" % CMVN_MAX_ROWS)
+        st = np.ascontiguousarray(st, dtype=np.float64)
+        rows = st.shape[1] - 1
+        shift, scale = np.zeros(rows, dtype=np.float32), np.zeros(rows, dtype=np.float32)
+        if not np.all(np.isfinite(st[0])) or not np.all(np.isfinite(st[1, :rows])) or \
+                lib().clx_cmvn_from_stats(_np_ptr(st), rows, int(norm_vars), _np_ptr(shift), _np_ptr(scale)) != OK:
+            raise ValueError("Cmvn: stats must be finite, with a count above 0")
+        return cls(shift=shift, scale=scale, pad=pad)
+
+    @classmethod
+    def sliding(cls, window=600, min_window=100, center=False, norm_vars=False, pad=0.0):
+        """Kaldi's apply-cmvn-sliding (its defaults): --cmn-window, --min-cmn-window (only read when not centred; at most window),
+        --center, --norm-vars."""
+        return cls(window=window, min_window=min_window, center=center, norm_vars=norm_vars, pad=pad)
+
+    @classmethod
+    def xvector(cls, pad=0.0):
+        """The x-vector / speaker-verification recipes' --cmn-window=300 --center=true --norm-vars=false."""
+        return cls.sliding(300, 100, True, False, pad)
+
+    @property
+    def shift(self):
+        return None if self._shift is None else self._shift.copy()
+
+    @property
+    def scale(self):
+        return None if self._scale is None else self._scale.copy()
+
+    def _sliding_opts(self):
+        return _CmvnSlidingOpts(self.window, self.min_window, int(self.center), int(self.norm_vars), self.pad, 0)
+
+    def _key(self):
+        if self.rows is not None:
+            return ("global", self._shift.tobytes(), self._scale.tobytes(), self.pad)
+        return ("sliding", self.window, self.min_window, self.center, self.norm_vars, self.pad)
+
+    def __repr__(self):
+        if self.rows is not None:
+            return "Cmvn.global_(<%d rows>, pad=%r)" % (self.rows, self.pad)
+        return "Cmvn.sliding(window=%d, min_window=%d, center=%r, norm_vars=%r, pad=%r)" % (self.window, self.min_window, self.center,
+                                                                                             self.norm_vars, self.pad)
+
+    def __eq__(self, other):
+        return isinstance(other, Cmvn) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+
 # ---- SpecAugment ----------------------------------------------------------------------------------------------------------------
 
 SPECAUG_MAX_MASKS = 32
@@ -2733,7 +2951,7 @@ class StreamSet:
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None, cmvn=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -2777,16 +2995,30 @@ class StreamSet:
         and in front of normalize= and augment=, which then see splice.n_out(n_out) rows, splice.frames_out(n_frames) frames and
         valid_frames' = splice.frames_out(valid_frames) -- FunASR's order: stacking, then CMVN, then masking.  The tensor returned
         is [B, splice.n_out(n_out), splice.frames_out(n_frames)] ("ct") or the same transposed ("tc"), with valid_frames'; the
-        frames behind them are splice.pad unless a later step says otherwise.  A later step that refuses the row count (normalize=
-        and augment= take 256 rows at most, so not the 560 of seven stacked 80-band frames) raises its own error.  The step is
-        out of place and the tensor it was made from is released on return, like read()'s scratch.  Whoever wants CMVN in front of
-        the deltas calls read_mel(normalize=) and then Context.splice_windows.  splice=None is the call without the argument."""
+        frames behind them are splice.pad unless a later step says otherwise.  A later step that refuses the row count raises its
+        own error: normalize= and augment= take 256 rows at most, so not the 560 of seven stacked 80-band frames; cmvn= takes up
+        to 8192 and is the route for more.  The step is out of place and the tensor it was made from is released on return, like
+        read()'s scratch.  Whoever wants CMVN in front of the deltas calls read_mel(normalize=) or read_mel(cmvn=) and then
+        Context.splice_windows.  splice=None is the call without the argument.
+
+        With cmvn=Cmvn... the features are normalised by statistics that are not the window's own: a global Cmvn (a fixed shift and
+        scale per row from a stats file: WeNet's global_cmvn, FunASR's am.mvn behind Splice.lfr()) by one clx_cmvn_global_windows
+        call in place, a sliding one (Kaldi's apply-cmvn-sliding; Cmvn.xvector() over MelSpec.mfcc is the x-vector front end) by one
+        clx_cmvn_sliding_windows call.  Either runs behind splice= and in front of augment=, over valid_frames' frames, and sets
+        the frames behind them to cmvn.pad; valid_frames and the shape do not change.  A global Cmvn's rows must be the call's row
+        count behind splice= (ValueError otherwise).  cmvn= and normalize= exclude each other (ValueError): one normaliser a call.
+        The sliding step is out of place and the tensor it was made from is released on return, like splice='s.  cmvn=None is the
+        call without the argument."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
         if augment is not None and not isinstance(augment, (SpecAugment, SpecAugmentPlan)):
             raise ValueError("read_mel: augment must be a SpecAugment, a SpecAugmentPlan or None, not %r" % (augment,))
         if splice is not None and not isinstance(splice, Splice):
             raise ValueError("read_mel: splice must be a Splice or None, not %r" % (splice,))
+        if cmvn is not None and not isinstance(cmvn, Cmvn):
+            raise ValueError("read_mel: cmvn must be a Cmvn or None, not %r" % (cmvn,))
+        if cmvn is not None and normalize is not None:
+            raise ValueError("read_mel: cmvn and normalize exclude each other: one normaliser a call")
         if add is not None and not isinstance(add, Add):
             raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
         if reverb is not None and not isinstance(reverb, Reverb):
@@ -2796,6 +3028,8 @@ class StreamSet:
             raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
         if not isinstance(spec, MelSpec) or spec._h is None or spec.ctx is not self.ctx:
             raise ValueError("read_mel: spec must be an open MelSpec of the set's context")
+        if cmvn is not None and cmvn.rows is not None and cmvn.rows != (spec.n_out if splice is None else splice.n_out(spec.n_out)):
+            raise ValueError("read_mel: the Cmvn has %d rows, the features %d" % (cmvn.rows, spec.n_out if splice is None else splice.n_out(spec.n_out)))
         if isinstance(n_frames, bool) or int(n_frames) != n_frames or int(n_frames) < 0:
             raise ValueError("read_mel: n_frames must be a whole number, not negative")
         n_frames = int(n_frames)
@@ -2825,6 +3059,8 @@ class StreamSet:
             rows, n_frames, vf = splice.n_out(rows), splice.frames_out(n_frames), splice.frames_out(vf)
         if normalize is not None:
             self.ctx.norm_windows(out, vf, _LAYOUTS[layout], normalize)
+        if cmvn is not None:
+            out = self.ctx.cmvn_windows(out, vf, _LAYOUTS[layout], cmvn)
         if augment is not None:
             plan = augment.draw(vf, rows) if isinstance(augment, SpecAugment) else augment
             _specaug_fit(plan, vf, rows, n_frames, "read_mel")

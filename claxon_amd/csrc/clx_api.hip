@@ -19,6 +19,7 @@
 #include "clx_reverb_fft.hip"
 #include "clx_specaug.hip"
 #include "clx_splice.hip"
+#include "clx_cmvn.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -337,6 +338,9 @@ struct clx_ctx {
     clx_call_scratch sa { "specaug", 64, sizeof(uint32_t), sizeof(uint32_t) };
     // clx_splice_windows (in 32-bit words): V per window, the plan's blocks and their coefficients
     clx_call_scratch sp { "splice", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    // clx_cmvn_global_windows and clx_cmvn_sliding_windows (one set for both; in 32-bit words): V per window, then the global
+    // call's shifts and scales
+    clx_call_scratch cmvn { "cmvn", 64, sizeof(uint32_t), sizeof(uint32_t) };
 };
 
 struct clx_mel_spec {
@@ -553,6 +557,7 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->rvf.release();
     ctx->sa.release();
     ctx->sp.release();
+    ctx->cmvn.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2021,6 +2026,55 @@ extern "C" int clx_splice_windows(clx_ctx* ctx, const void* d_in, void* d_out, s
 
 extern "C" int clx_splice_deltas(uint32_t order, uint32_t window, clx_splice_block* blocks, float* coefs, uint32_t* n_coefs) {
     return clx_splice_deltas_build(order, window, blocks, coefs, n_coefs) ? CLX_API_ERROR : CLX_OK;
+}
+
+extern "C" int clx_cmvn_global_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid, uint32_t layout,
+                                       const float* shift, const float* scale, const clx_cmvn_global_opts* opts, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_cmvn_plan pl;
+    const char* why = clx_cmvn_check_global(d_data, n_windows, rows, T, valid, layout, shift, scale, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    const size_t words = (size_t)pl.table_words;
+    clx_call_scratch& s = ctx->cmvn;
+    if (s.begin(ctx, stream, words) != CLX_OK) return CLX_API_ERROR;       // (the set has no device-only buffer)
+    clx_cmvn_fill_table((uint32_t*)s.h, n_windows, valid, rows, shift, scale);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    hipLaunchKernelGGL(clx_k_cmvn_global, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_cmvn::kThreads), 0, stream, (float*)d_data,
+                       (const uint32_t*)s.d, (uint32_t)n_windows, rows, T, opts->pad, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_cmvn_sliding_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T,
+                                        const uint32_t* valid, uint32_t layout, const clx_cmvn_sliding_opts* opts, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_cmvn_plan pl;
+    const char* why = clx_cmvn_check_sliding(d_in, d_out, n_windows, rows, T, valid, layout, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    const size_t words = (size_t)pl.table_words;
+    clx_call_scratch& s = ctx->cmvn;
+    if (s.begin(ctx, stream, words) != CLX_OK) return CLX_API_ERROR;       // (the set has no device-only buffer)
+    clx_cmvn_fill_table((uint32_t*)s.h, n_windows, valid, rows, nullptr, nullptr);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    hipLaunchKernelGGL(clx_k_cmvn_sliding, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_cmvn::kThreads), 0, stream, (const float*)d_in,
+                       (float*)d_out, (const uint32_t*)s.d, rows, T, opts->window, opts->center ? 1u : opts->min_window, opts->center,
+                       opts->norm_vars, opts->pad, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_cmvn_from_stats(const double* stats, uint32_t rows, uint32_t norm_vars, float* shift, float* scale) {
+    return clx_cmvn_from_stats_build(stats, rows, norm_vars, shift, scale) ? CLX_API_ERROR : CLX_OK;
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

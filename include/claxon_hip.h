@@ -894,6 +894,83 @@ typedef struct { uint32_t n_blocks, stride; float pad; uint32_t reserved; } clx_
 int  clx_splice_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
                         uint32_t layout, const clx_splice_block* blocks, const float* coefs, const clx_splice_opts* opts, void* stream);
 int  clx_splice_deltas(uint32_t order, uint32_t window, clx_splice_block* blocks, float* coefs, uint32_t* n_coefs);
+/* Global CMVN of a dense float32 feature batch on the device, in place: a fixed shift and scale per row, from a stats file
+ * (WeNet's global_cmvn, FunASR's am.mvn behind the low-frame-rate stacking, Kaldi's apply-cmvn with global statistics).  d_data is
+ * [n_windows][rows][T] (CLX_WINDOW_CT) or [n_windows][T][rows] (CLX_WINDOW_TC), rows in 1..8192 (the most clx_splice_windows can
+ * emit).  Window k has V = valid[k] <= T live frames.
+ *
+ *   plan       one launch (clx_k_cmvn_global), tiles of 1024 16-byte vectors of a window, 16-byte accesses where a vector lies
+ *              whole inside the window (and, on the load side, inside its live cells); no LDS.
+ *   live       for t < V, y = fl32(fl32(x + shift[r]) * scale[r]): two float32 operations, each rounded to nearest, never one
+ *              fused multiply-add.  That is word for word what (x + shift) * scale gives in numpy or torch float32, hence FunASR's
+ *              (x + means) * vars and WeNet's (x - mean) * istd with shift = -mean.  ESPnet's GlobalMVN divides, x / std, which is
+ *              another rounding and is not bit-equal to a multiplication by 1 / std.
+ *   padding    every cell with t >= V becomes the word of opts->pad; a window with V = 0 is all padding.
+ *   reads      no cell with t >= V is read, whatever it holds.
+ *   layouts    CT and TC of the same data give the same words.
+ *
+ * valid, shift and scale (rows float32 each) are host arrays, staged as clx_splice_windows stages its arrays (one pinned table a
+ * call -- V per window, then shift, then scale --, tables that have to grow replaced before anything is queued, one event behind
+ * the upload and one behind the launch), so the call is asynchronous on `stream` (NULL: the context's), returns without waiting
+ * for the device and the arrays may be reused at once.  CLX_API_ERROR, each with a clx_last_error text of its own, for
+ * opts == NULL, reserved bits, a pad that is not finite, an unknown layout, rows outside 1..8192, T above 2^31 - 1, shift == NULL,
+ * scale == NULL, a shift or a scale that is not finite, a null d_data or valid, a valid[k] > T and more than 2^31 - 1 tiles.
+ * n_windows == 0 or T == 0 succeeds and launches nothing.
+ *
+ * Sliding-window CMVN, out of place (Kaldi's apply-cmvn-sliding, the normaliser of the x-vector recipes): every live cell minus
+ * the mean of its row over a window of frames around (center) or up to (not center) its own, optionally divided by the standard
+ * deviation over the same frames.  d_in and d_out have one shape, as above; d_in is never written.
+ *
+ *   options    window N (1..1024; Kaldi's default 600), min_window M (1..N, only read when center == 0; Kaldi's 100), center and
+ *              norm_vars (0 or 1), pad.
+ *   window     for live frame t of a window with V live frames the statistics window [a, b) is Kaldi's SlidingWindowCmnInternal as
+ *              this project reads it (neither Kaldi nor torchaudio was run against it):
+ *                center:      a = t - N / 2 (whole-number division);  b = a + N
+ *                not center:  a = t - N;                              b = t + 1
+ *                if a < 0:             b -= a;  a = 0
+ *                if !center and b > t: b = max(t + 1, M)
+ *                if b > V:             a -= b - V;  b = V;  if a < 0: a = 0
+ *                n = b - a
+ *              so 0 <= a <= t < b <= V, and an uncentred window holds up to N + 1 frames.
+ *   ORDER      a row's sums S (of (double)x[u]) and Q (of (double)x[u] * (double)x[u], exact in double) over [a, b) are added up
+ *              in an order that is a function of (a, b, V) alone, never of the layout, the tile or the grid.  The time axis is cut
+ *              into groups of 32 frames from frame 0: G[k] is the double sum of (double)x[u] over u in [32 k, min(32 k + 32, V))
+ *              ascending from +0.0, H[k] the same over the squares.  With ka = ceil(a / 32) and kb = floor(b / 32): if ka <= kb, S
+ *              starts at +0.0 and adds x[a .. 32 ka) one by one ascending, then G[ka .. kb) ascending, then x[32 kb .. b)
+ *              ascending; otherwise S adds x[a .. b) ascending.  Q likewise with squares and H.  Every addition is a double
+ *              addition rounded once: at most 62 cell additions and 32 group additions a sum, instead of 1025.
+ *   live       m = S / (double)n; y = (double)x[t] - m; with norm_vars and n > 1 (n == 1: y stays; Kaldi sets the variance to 1):
+ *              v = Q / (double)n - m * m (a division, a product and a difference, each rounded once, none fused),
+ *              v = v < 1e-10 ? 1e-10 : v, y = y / sqrt(v) (a correctly rounded double square root and division).  The cell is
+ *              (float)y, one rounding.  Cells that are not finite give what IEEE gives inside the windows that reach them, and
+ *              nothing elsewhere.
+ *   padding    a frame t >= V is the word of opts->pad in every row; a window with V = 0 is all padding.
+ *   reads      no cell of d_in outside the frames [0, V) of its window is read, whatever it holds.
+ *   layouts    CT and TC of the same data give the same words.
+ *   plan       one launch (clx_k_cmvn_sliding): a block is a tile of 256 output frames of one window; it stages the tile's source
+ *              span [32 floor(a(first frame) / 32), b(last live frame)), at most 1311 frames, of 8 rows at a time as floats in
+ *              LDS with the span's whole groups' G and H as doubles beside them (48 608 bytes: three workgroups a CU); a tile whose
+ *              frames are all padding writes the pad and stages nothing.
+ *
+ * valid is staged as above (the table is V per window).  CLX_API_ERROR, each with a text of its own, for opts == NULL, reserved
+ * bits, a pad that is not finite, an unknown layout, rows outside 1..8192, T above 2^31 - 1, window outside 1..1024, center or
+ * norm_vars above 1, with center == 0 a min_window outside 1..window, a null d_in, d_out or valid, d_out == d_in, a valid[k] > T
+ * and more than 2^31 - 1 tiles.  n_windows == 0 or T == 0 succeeds and launches nothing.  Not here: windows above 1024 frames,
+ * accumulating the statistics of a corpus, Kaldi's VAD.
+ *
+ * clx_cmvn_from_stats (host only, no context) turns Kaldi's CMVN accumulator into shift and scale: stats is [2][rows + 1] doubles,
+ * row 0 the sums and the count, row 1 the sums of squares (its last entry unused).  mean = sum / count,
+ * var = max(sumsq / count - mean * mean, 1e-20) (ApplyCmvn's floor), shift = -mean, scale = norm_vars ? 1 / sqrt(var) : 1, all in
+ * double, each result rounded once to float32.  Kaldi itself applies x * scale + offset with offset = -mean * scale, which rounds
+ * differently from (x + shift) * scale: the two agree to float32 rounding, not word for word.  CLX_API_ERROR for a null argument,
+ * rows outside 1..8192, norm_vars above 1, a count that is not above 0 and statistics that give a shift or scale that is not finite. */
+typedef struct { float pad; uint32_t reserved; } clx_cmvn_global_opts;
+typedef struct { uint32_t window, min_window, center, norm_vars; float pad; uint32_t reserved; } clx_cmvn_sliding_opts;
+int  clx_cmvn_global_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                             uint32_t layout, const float* shift, const float* scale, const clx_cmvn_global_opts* opts, void* stream);
+int  clx_cmvn_sliding_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T,
+                              const uint32_t* valid, uint32_t layout, const clx_cmvn_sliding_opts* opts, void* stream);
+int  clx_cmvn_from_stats(const double* stats, uint32_t rows, uint32_t norm_vars, float* shift, float* scale);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
