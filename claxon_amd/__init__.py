@@ -104,12 +104,13 @@ EXPORTS = [
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
     "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
     "clx_splice_windows", "clx_splice_deltas", "clx_cmvn_global_windows", "clx_cmvn_sliding_windows", "clx_cmvn_from_stats",
+    "clx_vad_windows", "clx_select_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_vad.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -206,6 +207,8 @@ def lib():
     L.clx_cmvn_global_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_cmvn_sliding_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]
     L.clx_cmvn_from_stats.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.clx_vad_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
+    L.clx_select_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
     L.clx_batch_slots.argtypes = [vp]
     L.clx_batch_set_profiling.argtypes = [vp, C.c_int]
@@ -1048,6 +1051,88 @@ class Context:
         opts = cmvn._sliding_opts()
         self._check(lib().clx_cmvn_sliding_windows(self._h, d_ptr, o_ptr, B, rows, T, _np_ptr(valid), int(layout), C.byref(opts), handle))
         return out
+
+    def _feature_batch(self, who, data, valid, layout, stream):
+        """(pointer, B, rows, T, valid as uint32, stream handle) of a dense float32 feature batch: a CUDA tensor or a (pointer, B, rows,
+        T) tuple, as the *_windows methods take them."""
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("%s: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor" % who)
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("%s: %s is out of range" % (who, name))
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("%s: valid has %d entries for %d windows" % (who, valid.size, B))
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        return d_ptr, B, rows, T, valid, (C.c_void_p(handle) if handle else None)
+
+    def vad_windows(self, data, valid, layout, vad, mask=None, thresholds=None, stream=None):
+        """clx_vad_windows: Kaldi's energy VAD (compute-vad, as this project reads it) over row vad.row of the dense float32 feature
+        batch `data` -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows 1..8192 -- and the first valid[k] frames of window
+        k: byte 1 for a voiced frame, 0 for an unvoiced one and for every frame from valid[k] on (claxon_hip.h has the definition and
+        the order of the sum behind the threshold).  `vad` is a Vad; its select and pad are not read here.  mask is a uint8 [B, T]
+        CUDA tensor (None: a new one), thresholds an optional float32 [B] CUDA tensor that receives each window's threshold; with a
+        (pointer, B, rows, T) tuple for `data` both are pointers and mask must be given.  `data` is not written; nothing of it from
+        valid[k] on and no other row is read.  Asynchronous on `stream` as gather_windows is.  Returns mask."""
+        if not isinstance(vad, Vad):
+            raise ValueError("vad_windows: vad must be a Vad, not %r" % (vad,))
+        d_ptr, B, rows, T, valid, handle = self._feature_batch("vad_windows", data, valid, layout, stream)
+        if vad.row >= rows:
+            raise ValueError("vad_windows: the Vad reads row %d, the batch has %d" % (vad.row, rows))
+        if hasattr(data, "data_ptr") and mask is None:
+            import torch
+            mask = torch.empty((B, T), dtype=torch.uint8, device=data.device)
+        if hasattr(mask, "data_ptr"):
+            if tuple(mask.shape) != (B, T) or not mask.is_contiguous() or str(mask.dtype) != "torch.uint8":
+                raise ValueError("vad_windows: mask must be a contiguous uint8 tensor of shape %r" % ((B, T),))
+        if hasattr(thresholds, "data_ptr"):
+            if tuple(thresholds.shape) != (B,) or not thresholds.is_contiguous() or str(thresholds.dtype) != "torch.float32":
+                raise ValueError("vad_windows: thresholds must be a contiguous float32 [B] tensor")
+        m_ptr = mask.data_ptr() if hasattr(mask, "data_ptr") else (int(mask) if mask else None)
+        t_ptr = thresholds.data_ptr() if hasattr(thresholds, "data_ptr") else (int(thresholds) if thresholds else None)
+        opts = vad._opts()
+        self._check(lib().clx_vad_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), int(layout), C.byref(opts), m_ptr, t_ptr, handle))
+        return mask
+
+    def select_windows(self, data, valid, mask, layout, pad=0.0, out=None, stream=None):
+        """clx_select_windows: of the first valid[k] frames of window k of the dense float32 feature batch `data` -- [B, rows, T]
+        (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows 1..8192 -- those whose byte of `mask` (uint8 [B, T]: vad_windows', or any
+        other) is not 0, moved to the front in their order, every row's words as they are; the frames behind them are `pad`.  Out
+        of place: `out` has data's shape and must not overlap it (None: a new tensor); `data` is not written, and neither it nor
+        the mask is read from valid[k] on.  `data`, `mask` and `out` are CUDA tensors, or `data` is a (pointer, B, rows, T) tuple and
+        the other two pointers.  Returns (out, counts): counts[k] (a host int64 numpy array) is the number of frames kept, the new
+        valid[k]; 0 is a window that is all pad.  THE CALL WAITS for its own launches and for those B words to arrive; everything
+        else here is asynchronous on `stream` as gather_windows is."""
+        d_ptr, B, rows, T, valid, handle = self._feature_batch("select_windows", data, valid, layout, stream)
+        if isinstance(pad, bool) or not isinstance(pad, (int, float, np.integer, np.floating)):
+            raise ValueError("select_windows: pad must be a number, not %r" % (pad,))
+        shape = (B, T, rows) if int(layout) == WINDOW_TC else (B, rows, T)
+        if hasattr(mask, "data_ptr"):
+            if tuple(mask.shape) != (B, T) or not mask.is_contiguous() or str(mask.dtype) != "torch.uint8":
+                raise ValueError("select_windows: mask must be a contiguous uint8 tensor of shape %r" % ((B, T),))
+        if hasattr(data, "data_ptr") and out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        if hasattr(out, "data_ptr"):
+            if not hasattr(data, "data_ptr") or tuple(out.shape) != shape or not out.is_contiguous() or str(out.dtype) != "torch.float32":
+                raise ValueError("select_windows: out must be a contiguous float32 tensor of shape %r" % (shape,))
+        m_ptr = mask.data_ptr() if hasattr(mask, "data_ptr") else (int(mask) if mask else None)
+        o_ptr = out.data_ptr() if hasattr(out, "data_ptr") else (int(out) if out else None)
+        with np.errstate(over="ignore"):
+            opts = _SelectOpts(float(np.float32(pad)), (C.c_uint32 * 3)(0, 0, 0))
+        counts = np.zeros(B, dtype=np.uint32)
+        self._check(lib().clx_select_windows(self._h, d_ptr, o_ptr, B, rows, T, _np_ptr(valid), m_ptr, int(layout), C.byref(opts), None,
+                                             _np_ptr(counts) if B else None, handle))
+        return out, counts.astype(np.int64)
 
     def decode_subframes(self, arena, offs, block_sizes, bps, out_offs, out=None):
         a = _u8(arena)
@@ -2356,6 +2441,82 @@ class Cmvn:
         return hash(self._key())
 
 
+# ---- energy VAD and frame selection ------------------------------------------------------------------------------------------------
+
+VAD_MAX_CONTEXT, VAD_MAX_ROWS = 128, 8192
+
+
+class _VadOpts(C.Structure):             # clx_vad_opts
+    _fields_ = [("energy_threshold", C.c_float), ("energy_mean_scale", C.c_float), ("frames_context", C.c_uint32),
+                ("proportion_threshold", C.c_float), ("row", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class _SelectOpts(C.Structure):          # clx_select_opts
+    _fields_ = [("pad", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+def _vad_f32(v, what):
+    """`v` as the float32 value the C side is given: a finite number."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) \
+            or abs(float(v)) > float(np.finfo(np.float32).max):
+        raise ValueError("Vad: %s must be a finite number, not %r" % (what, v))
+    return float(np.float32(v))
+
+
+def _vad_whole(v, lo, hi, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError("Vad: %s must be a whole number in %d..%d, not %r" % (what, lo, hi, v))
+    return int(v)
+
+
+class Vad:
+    """What Context.vad_windows and read_mel(..., vad=) decide for every frame: Kaldi's energy VAD (compute-vad) as this project
+    reads it.  A plain value: it owns nothing on the device.  A frame's cell e of row `row` (0: C0, or the log energy, of
+    MelSpec.mfcc) is above when e > energy_threshold + energy_mean_scale * (the mean of that row over the window's valid frames);
+    the frame is voiced when at least proportion_threshold of the frames within frames_context of it (cut at the window's ends)
+    are above.  The defaults are Kaldi's (5.0, 0.5, 0, 0.6); voxceleb() is conf/vad.conf of the VoxCeleb and SRE16 recipes (5.5,
+    0.5, 2, 0.12).  select (read_mel only): keep the voiced frames alone, moved to the front (select-voiced-frames), the frames
+    behind them set to pad; select=False only decides.  ValueError for an energy_threshold, energy_mean_scale or pad that is not a
+    finite float32 number, a frames_context outside 0..128, a proportion_threshold that is not above 0 and below 1, a row outside
+    0..8191 and a select that is not 0 / 1."""
+
+    def __init__(self, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6, row=0, select=True, pad=0.0):
+        self.energy_threshold = _vad_f32(energy_threshold, "energy_threshold")
+        self.energy_mean_scale = _vad_f32(energy_mean_scale, "energy_mean_scale")
+        self.frames_context = _vad_whole(frames_context, 0, VAD_MAX_CONTEXT, "frames_context")
+        if isinstance(proportion_threshold, (bool, np.bool_)) or not isinstance(proportion_threshold, (int, float, np.integer, np.floating)) \
+                or not 0.0 < float(np.float32(proportion_threshold)) < 1.0:
+            raise ValueError("Vad: proportion_threshold must be above 0 and below 1, not %r" % (proportion_threshold,))
+        self.proportion_threshold = float(np.float32(proportion_threshold))
+        self.row = _vad_whole(row, 0, VAD_MAX_ROWS - 1, "row")
+        if not isinstance(select, (bool, int, np.integer, np.bool_)) or int(select) not in (0, 1):
+            raise ValueError("Vad: select must be 0 or 1, not %r" % (select,))
+        self.select = bool(select)
+        self.pad = _vad_f32(pad, "pad")
+
+    @classmethod
+    def voxceleb(cls, row=0, select=True, pad=0.0):
+        """conf/vad.conf of Kaldi's VoxCeleb and SRE16 recipes: --vad-energy-threshold=5.5 --vad-energy-mean-scale=0.5
+        --vad-frames-context=2 --vad-proportion-threshold=0.12."""
+        return cls(5.5, 0.5, 2, 0.12, row, select, pad)
+
+    def _opts(self):
+        return _VadOpts(self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold, self.row,
+                        (C.c_uint32 * 3)(0, 0, 0))
+
+    def _key(self):
+        return (self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold, self.row, self.select, self.pad)
+
+    def __repr__(self):
+        return "Vad(energy_threshold=%r, energy_mean_scale=%r, frames_context=%d, proportion_threshold=%r, row=%d, select=%r, pad=%r)" % self._key()
+
+    def __eq__(self, other):
+        return isinstance(other, Vad) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+
 # ---- SpecAugment ----------------------------------------------------------------------------------------------------------------
 
 SPECAUG_MAX_MASKS = 32
@@ -2951,7 +3112,7 @@ class StreamSet:
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None, cmvn=None):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None, cmvn=None, vad=None, return_vad=False):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -3008,7 +3169,21 @@ class StreamSet:
         the frames behind them to cmvn.pad; valid_frames and the shape do not change.  A global Cmvn's rows must be the call's row
         count behind splice= (ValueError otherwise).  cmvn= and normalize= exclude each other (ValueError): one normaliser a call.
         The sliding step is out of place and the tensor it was made from is released on return, like splice='s.  cmvn=None is the
-        call without the argument."""
+        call without the argument.
+
+        With vad=Vad(...) the frames are judged voiced or not by Kaldi's energy VAD (compute-vad; Vad.voxceleb() over MelSpec.mfcc
+        with cmvn=Cmvn.xvector() is the x-vector front end): one clx_vad_windows call over row vad.row of the batch as it stands
+        behind splice= and IN FRONT OF normalize= / cmvn= -- Kaldi computes the VAD on the raw MFCCs -- over valid_frames' frames.
+        With vad.select (the default) the voiced frames alone are then kept, moved to the front (select-voiced-frames): one
+        clx_select_windows call BEHIND normalize= / cmvn= -- apply-cmvn-sliding runs over all frames, then the selection -- and
+        in front of augment=.  The tensor returned is the selected one, of the same shape: its valid_frames are the numbers of
+        voiced frames (0 for a window without one: Kaldi skips such an utterance, here it is all pad), the frames behind them are
+        vad.pad, augment= draws its plan from those counts, and the tensor it was made from is released on return.  THE CALL THEN
+        WAITS for the device once, for B words (the counts): the one step of read_mel whose result the host needs.  With
+        select=False the features and valid_frames are untouched and nothing waits.  return_vad=True appends the mask (uint8
+        [B, n_frames] on the GPU) to the return value: its time axis is the one before the selection, and its bytes from
+        valid_frames on are 0.  ValueError for a vad that is not a Vad, a vad.row that is not below the row count behind splice=,
+        and return_vad=True without vad=.  vad=None is the call without the argument."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
         if augment is not None and not isinstance(augment, (SpecAugment, SpecAugmentPlan)):
@@ -3019,6 +3194,10 @@ class StreamSet:
             raise ValueError("read_mel: cmvn must be a Cmvn or None, not %r" % (cmvn,))
         if cmvn is not None and normalize is not None:
             raise ValueError("read_mel: cmvn and normalize exclude each other: one normaliser a call")
+        if vad is not None and not isinstance(vad, Vad):
+            raise ValueError("read_mel: vad must be a Vad or None, not %r" % (vad,))
+        if return_vad and vad is None:
+            raise ValueError("read_mel: return_vad=True needs vad=")
         if add is not None and not isinstance(add, Add):
             raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
         if reverb is not None and not isinstance(reverb, Reverb):
@@ -3030,6 +3209,8 @@ class StreamSet:
             raise ValueError("read_mel: spec must be an open MelSpec of the set's context")
         if cmvn is not None and cmvn.rows is not None and cmvn.rows != (spec.n_out if splice is None else splice.n_out(spec.n_out)):
             raise ValueError("read_mel: the Cmvn has %d rows, the features %d" % (cmvn.rows, spec.n_out if splice is None else splice.n_out(spec.n_out)))
+        if vad is not None and vad.row >= (spec.n_out if splice is None else splice.n_out(spec.n_out)):
+            raise ValueError("read_mel: the Vad reads row %d, the features have %d" % (vad.row, spec.n_out if splice is None else splice.n_out(spec.n_out)))
         if isinstance(n_frames, bool) or int(n_frames) != n_frames or int(n_frames) < 0:
             raise ValueError("read_mel: n_frames must be a whole number, not negative")
         n_frames = int(n_frames)
@@ -3057,16 +3238,21 @@ class StreamSet:
         if splice is not None:
             out = self.ctx.splice_windows(out, vf, _LAYOUTS[layout], splice)
             rows, n_frames, vf = splice.n_out(rows), splice.frames_out(n_frames), splice.frames_out(vf)
+        mask = None
+        if vad is not None:                                  # (queued in front of the normaliser, which may work in place)
+            mask = self.ctx.vad_windows(out, vf, _LAYOUTS[layout], vad)
         if normalize is not None:
             self.ctx.norm_windows(out, vf, _LAYOUTS[layout], normalize)
         if cmvn is not None:
             out = self.ctx.cmvn_windows(out, vf, _LAYOUTS[layout], cmvn)
+        if vad is not None and vad.select:
+            out, vf = self.ctx.select_windows(out, vf, mask, _LAYOUTS[layout], vad.pad)
         if augment is not None:
             plan = augment.draw(vf, rows) if isinstance(augment, SpecAugment) else augment
             _specaug_fit(plan, vf, rows, n_frames, "read_mel")
             if B and n_frames:
                 out = self.ctx.specaug_windows(out, vf, _LAYOUTS[layout], plan.warp, plan.freq_masks, plan.time_masks, plan.fill)
-        return out, torch.from_numpy(vf)
+        return (out, torch.from_numpy(vf)) + ((mask,) if return_vad else ())
 
 
 def open_streams(ctx, streams):

@@ -20,6 +20,7 @@
 #include "clx_specaug.hip"
 #include "clx_splice.hip"
 #include "clx_cmvn.hip"
+#include "clx_vad.hip"                  // (behind clx_norm.hip: the energy sum is that file's)
 
 #include <algorithm>
 #include <cstdio>
@@ -341,6 +342,10 @@ struct clx_ctx {
     // clx_cmvn_global_windows and clx_cmvn_sliding_windows (one set for both; in 32-bit words): V per window, then the global
     // call's shifts and scales
     clx_call_scratch cmvn { "cmvn", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    // clx_vad_windows and clx_select_windows (one set for both; in 32-bit words): V per window; the selection then keeps, on the
+    // device only, count per window, the tile counts and the tile bases, and in the staging behind V the counts on their way to
+    // the host.  Beside it the decision's partial sums
+    clx_call_scratch vad { "vad", 64, sizeof(uint32_t), sizeof(uint32_t) };
 };
 
 struct clx_mel_spec {
@@ -558,6 +563,7 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->sa.release();
     ctx->sp.release();
     ctx->cmvn.release();
+    ctx->vad.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2075,6 +2081,76 @@ extern "C" int clx_cmvn_sliding_windows(clx_ctx* ctx, const void* d_in, void* d_
 
 extern "C" int clx_cmvn_from_stats(const double* stats, uint32_t rows, uint32_t norm_vars, float* shift, float* scale) {
     return clx_cmvn_from_stats_build(stats, rows, norm_vars, shift, scale) ? CLX_API_ERROR : CLX_OK;
+}
+
+extern "C" int clx_vad_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid, uint32_t layout,
+                               const clx_vad_opts* opts, void* d_mask, void* d_thresholds, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_vad_plan pl;
+    const char* why = clx_vad_check(d_data, n_windows, rows, T, valid, layout, opts, d_mask, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    clx_call_scratch& s = ctx->vad;
+    if (s.begin(ctx, stream, (size_t)pl.table_words, (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;   // (s == 0: 0 partial sums, reserved all the same)
+    memcpy(s.h, valid, n_windows * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    if (pl.sum_blocks) {
+        hipLaunchKernelGGL(clx_k_vad_sum, dim3(pl.sum_blocks), dim3(clx_vad::kThreads), 0, stream, (const float*)d_data, (const uint32_t*)s.d,
+                           (double*)s.part.p, rows, T, opts->row, pl.tc, pl.n_chunks, (uint64_t)n_windows * pl.n_chunks);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(clx_k_vad_decide, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_vad::kThreads), 0, stream, (const float*)d_data,
+                       (const uint32_t*)s.d, (const double*)s.part.p, (uint8_t*)d_mask, (float*)d_thresholds, *opts, rows, T, pl.tc, pl.n_chunks,
+                       pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_select_windows(clx_ctx* ctx, const void* d_src, void* d_dst, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                  const void* d_mask, uint32_t layout, const clx_select_opts* opts, void* d_counts, uint32_t* counts,
+                                  void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_vad_plan pl;
+    const char* why = clx_select_check(d_src, d_dst, n_windows, rows, T, valid, d_mask, layout, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_tiles == 0) {
+        if (counts) memset(counts, 0, n_windows * sizeof(uint32_t));
+        return CLX_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    clx_call_scratch& s = ctx->vad;
+    if (s.begin(ctx, stream, (size_t)pl.table_words, 0) != CLX_OK) return CLX_API_ERROR;   // (no partial sums of its own: reserved with need 0)
+    memcpy(s.h, valid, n_windows * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, n_windows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    uint32_t* const d_valid = (uint32_t*)s.d;
+    uint32_t* const d_count = d_valid + n_windows;
+    uint32_t* const d_tile_counts = d_count + n_windows;
+    uint32_t* const d_tile_base = d_tile_counts + n_windows * (size_t)pl.n_tiles;
+    uint32_t pad_word;
+    memcpy(&pad_word, &opts->pad, sizeof pad_word);
+    const dim3 grid((unsigned)(n_windows * pl.n_tiles)), block(clx_vad::kThreads);
+    hipLaunchKernelGGL(clx_k_select_rank, grid, block, 0, stream, (const uint8_t*)d_mask, (const uint32_t*)d_valid, d_tile_counts, T, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_select_scan, dim3(pl.scan_blocks), block, 0, stream, (const uint32_t*)d_tile_counts, d_tile_base, d_count,
+                       (uint32_t*)d_counts, (uint32_t)n_windows, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_select_move, grid, block, 0, stream, (const uint32_t*)d_src, (uint32_t*)d_dst, (const uint8_t*)d_mask,
+                       (const uint32_t*)d_valid, (const uint32_t*)d_tile_base, (const uint32_t*)d_count, rows, T, pad_word, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t* const h_count = (uint32_t*)s.h + n_windows;                  // (the staging behind V: nothing uploads from there)
+    if (counts) HIP_TRY(ctx, hipMemcpyAsync(h_count, d_count, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, s.done(stream));
+    if (counts) {                                              // the one wait: for this call's own launches and its copy of n_windows words
+        HIP_TRY(ctx, hipEventSynchronize(s.ev_done));
+        memcpy(counts, h_count, n_windows * sizeof(uint32_t));
+    }
+    return CLX_OK;
 }
 
 extern "C" int clx_batch_results(clx_batch* b, clx_frame_result* results) {

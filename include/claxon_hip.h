@@ -956,7 +956,7 @@ int  clx_splice_deltas(uint32_t order, uint32_t window, clx_splice_block* blocks
  * bits, a pad that is not finite, an unknown layout, rows outside 1..8192, T above 2^31 - 1, window outside 1..1024, center or
  * norm_vars above 1, with center == 0 a min_window outside 1..window, a null d_in, d_out or valid, d_out == d_in, a valid[k] > T
  * and more than 2^31 - 1 tiles.  n_windows == 0 or T == 0 succeeds and launches nothing.  Not here: windows above 1024 frames,
- * accumulating the statistics of a corpus, Kaldi's VAD.
+ * accumulating the statistics of a corpus.  (Kaldi's VAD is clx_vad_windows below.)
  *
  * clx_cmvn_from_stats (host only, no context) turns Kaldi's CMVN accumulator into shift and scale: stats is [2][rows + 1] doubles,
  * row 0 the sums and the count, row 1 the sums of squares (its last entry unused).  mean = sum / count,
@@ -971,6 +971,65 @@ int  clx_cmvn_global_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint3
 int  clx_cmvn_sliding_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T,
                               const uint32_t* valid, uint32_t layout, const clx_cmvn_sliding_opts* opts, void* stream);
 int  clx_cmvn_from_stats(const double* stats, uint32_t rows, uint32_t norm_vars, float* shift, float* scale);
+/* Kaldi's energy VAD over one row of a dense float32 feature batch on the device (compute-vad), and the selection of the frames a
+ * byte mask names (select-voiced-frames, or any other mask: a neural VAD's).  d_data is [n_windows][rows][n_frames] (CLX_WINDOW_CT)
+ * or [n_windows][n_frames][rows] (CLX_WINDOW_TC), rows 1..8192; valid[k] <= n_frames is window k's live frames V.
+ *
+ * The decision, clx_vad_windows: d_mask is [n_windows][n_frames] bytes, d_thresholds (may be NULL) [n_windows] floats.
+ *
+ *   options    float32 energy_threshold E (Kaldi's default 5.0) and energy_mean_scale s (0.5), frames_context c (0..128; 0) and
+ *              float32 proportion_threshold p (0 < p < 1; 0.6); row r < rows, the energy row (0: C0 or the log energy of a Kaldi
+ *              MFCC); reserved words, 0.  conf/vad.conf of the VoxCeleb and SRE16 recipes: 5.5, 0.5, 2, 0.12.
+ *   energy     e[t] is the cell at (row r, frame t) of the window.
+ *   SUM        S is the double sum of (double)e[0 .. V) in clx_norm_windows' order: chunks of 4096 frames; inside a chunk strand
+ *              i of 64 adds the cells t = i mod 64 ascending from +0.0; the strands fold by xor 32, 16, 8, 4, 2, 1; the chunks
+ *              that hold a live frame add up ascending from +0.0.  Every addition is a double addition rounded once.  The same
+ *              function of the cells in CT and TC.
+ *   threshold  s == 0 (Kaldi's `if (mean_scale != 0)`) or V == 0: thr = E, and with s == 0 nothing is summed and no sum kernel is
+ *              launched.  Otherwise thr = (float)(E + s * (S / V)): E, s and V as doubles, a division, a product and a sum, each
+ *              rounded once to double, none fused, then one rounding to float32.
+ *   above      above[u] = e[u] > thr, a float32 compare: false for a NaN on either side, false for a cell equal to thr.
+ *   decision   for t < V: lo = max(t - c, 0), hi = min(t + c, V - 1), den = hi - lo + 1, num = the number of above[u] over
+ *              lo <= u <= hi; the byte is ((float)num >= fl32((float)den * p)) ? 1 : 0, one float32 product rounded once.  For
+ *              t >= V the byte is 0.
+ *   reads      no cell at t >= V and no cell of another row is read, whatever it holds.
+ *   outputs    every byte of d_mask is written once; d_thresholds[k] = thr.  d_data is not written.
+ * This is Kaldi's ComputeVadEnergy as this project reads it.  Kaldi sums the energies and forms the threshold in float32, so a cell
+ * within an ulp or so of the threshold may fall the other way there; no Kaldi binary was run against this.
+ *   plan       clx_k_vad_sum (a wave a chunk of a window's energy row; skipped when s == 0), then clx_k_vad_decide: a block is a
+ *              tile of 256 frames; it folds the partial sums into thr, takes the `above` flags of the tile and its context (512
+ *              frames at most) with ballots, leaves an inclusive prefix count in LDS (2 080 bytes) and forms num as the difference
+ *              of two entries: no lane loops over the context.
+ * CLX_API_ERROR, each with a clx_last_error text of its own, for opts == NULL, reserved words, an E or s that is not finite, a p
+ * outside (0, 1) or not finite, c above 128, an unknown layout, rows outside 1..8192, n_frames above 2^31 - 1, row >= rows, a null
+ * d_data, valid or d_mask, a valid[k] > n_frames and more than 2^31 - 1 tiles.  n_windows == 0 or n_frames == 0 succeeds and
+ * launches nothing.
+ *
+ * The selection, clx_select_windows, out of place: frame t < V of window k is selected when d_mask[k][t] != 0; bytes at t >= V are
+ * never read.  count is the number of selected frames.  Output frame j < count holds the words of source frame t_j, the j-th
+ * selected frame in ascending order: a copy of 32-bit words over all rows, so NaN payloads survive.  Output frames count <= j <
+ * n_frames hold the word of opts->pad in every row (any float32 value).  d_dst has d_src's shape and must not overlap it; every
+ * cell of d_dst is written exactly once, d_src is not written and no cell of it at t >= V is read.  CT and TC give the same words.
+ * count == 0 is a window that is all pad, not an error (Kaldi skips such an utterance).  d_counts (device uint32 [n_windows], may
+ * be NULL) receives the counts.
+ *   plan       clx_k_select_rank (a block a tile of 256 source frames: ballots, the tile's popcount), clx_k_select_scan (a wave a
+ *              window: the exclusive scan of the tile counts, and count), clx_k_select_move (a block a source tile: ranks from the
+ *              ballots, the tile's selected frames listed in LDS, 1 040 bytes, then lanes along the output's contiguous axis; the
+ *              block also writes the pad of its own 256 output frames).
+ * With counts (HOST uint32 [n_windows], may be NULL) the call copies the counts into it and RETURNS ONCE THEY HAVE ARRIVED, through
+ * the pinned staging of its scratch set and a wait on the event behind its own launches: the one window entry point that waits for
+ * the device.  Without counts it is asynchronous like the others.
+ * CLX_API_ERROR, each with a text of its own, for opts == NULL, reserved words, an unknown layout, rows outside 1..8192, n_frames
+ * above 2^31 - 1, a null d_src, d_dst, valid or d_mask, a valid[k] > n_frames, more than 2^31 - 1 tiles and a d_dst that overlaps
+ * d_src.  n_windows == 0 or n_frames == 0 succeeds and launches nothing (counts is then zeros, d_counts is not written).
+ * Both calls stage valid[] as the calls above do and share one scratch set. */
+typedef struct { float energy_threshold, energy_mean_scale; uint32_t frames_context; float proportion_threshold; uint32_t row; uint32_t reserved[3]; } clx_vad_opts;
+typedef struct { float pad; uint32_t reserved[3]; } clx_select_opts;
+int  clx_vad_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t n_frames, const uint32_t* valid,
+                     uint32_t layout, const clx_vad_opts* opts, void* d_mask, void* d_thresholds, void* stream);
+int  clx_select_windows(clx_ctx* ctx, const void* d_src, void* d_dst, size_t n_windows, uint32_t rows, uint32_t n_frames,
+                        const uint32_t* valid, const void* d_mask, uint32_t layout, const clx_select_opts* opts, void* d_counts,
+                        uint32_t* counts, void* stream);
 /* Number of predictor slots (subframes incl. alignment padding) in the plan. */
 uint64_t clx_batch_slots(const clx_batch* b);
 /* Per-kernel HIP-event timing: kernels are numbered in launch order (clx_batch_kernel_name gives the name; NULL past the last
