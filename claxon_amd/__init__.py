@@ -104,13 +104,13 @@ EXPORTS = [
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
     "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
     "clx_splice_windows", "clx_splice_deltas", "clx_cmvn_global_windows", "clx_cmvn_sliding_windows", "clx_cmvn_from_stats",
-    "clx_vad_windows", "clx_select_windows",
+    "clx_vad_windows", "clx_select_windows", "clx_cmvn_stats_windows", "clx_cmvn_grouped_windows",
 ]
 
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_vad.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_cmvn_stats.hip", "clx_vad.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -207,6 +207,8 @@ def lib():
     L.clx_cmvn_global_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_cmvn_sliding_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]
     L.clx_cmvn_from_stats.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.clx_cmvn_stats_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+    L.clx_cmvn_grouped_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_vad_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_select_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_batch_slots.restype = C.c_uint64
@@ -1002,16 +1004,21 @@ class Context:
                                              _np_ptr(coefs) if coefs.size else None, C.byref(opts), C.c_void_p(handle) if handle else None))
         return out
 
-    def cmvn_windows(self, data, valid, layout, cmvn, out=None, stream=None):
+    def cmvn_windows(self, data, valid, layout, cmvn, out=None, stream=None, groups=None):
         """clx_cmvn_global_windows or clx_cmvn_sliding_windows, as `cmvn` (a Cmvn) says, over the dense float32 feature batch `data`
         -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), rows 1..8192 -- and the first valid[k] frames of window k
         (claxon_hip.h has the definitions, the statistics window and the order of the sums); every frame from valid[k] on becomes
         cmvn.pad.  A global Cmvn (cmvn.rows == rows) works in place: `out` must be None, and `data` is returned.  A sliding one is
         out of place: `out` has data's shape and must not be data (None: a new tensor), `data` is not written and nothing of it
         from valid[k] on is read; `out` is returned.  `data` and `out` are CUDA float32 tensors, or `data` is a (pointer, B, rows, T)
-        tuple and `out` a pointer.  Asynchronous on `stream` as gather_windows is."""
+        tuple and `out` a pointer.  A grouped Cmvn (Cmvn.grouped(stats)) works in place like a global one, by
+        clx_cmvn_grouped_windows: window k is normalised by the accumulator of group groups[k] of the Cmvn's CmvnStats as it stands
+        when the launch runs (-1: the window keeps its live cells and gets its padding; groups=None: every window group 0, for a
+        CmvnStats of one group only).  groups= goes with a grouped Cmvn alone.  Asynchronous on `stream` as gather_windows is."""
         if not isinstance(cmvn, Cmvn):
             raise ValueError("cmvn_windows: cmvn must be a Cmvn, not %r" % (cmvn,))
+        if groups is not None and cmvn._stats is None:
+            raise ValueError("cmvn_windows: groups= goes with a grouped Cmvn (Cmvn.grouped), not %r" % (cmvn,))
         tc = int(layout) == WINDOW_TC
         if hasattr(data, "data_ptr"):
             if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
@@ -1031,6 +1038,20 @@ class Context:
             stream = torch.cuda.current_stream(data.device)
         handle = getattr(stream, "cuda_stream", stream)
         handle = C.c_void_p(handle) if handle else None
+        if cmvn._stats is not None:
+            st = cmvn._stats
+            st._open("a grouped Cmvn")
+            if out is not None:
+                raise ValueError("cmvn_windows: a grouped Cmvn works in place: out must be None")
+            if cmvn.rows != rows:
+                raise ValueError("cmvn_windows: the Cmvn has %d rows, the batch %d" % (cmvn.rows, rows))
+            if groups is None and st.groups > 1:
+                raise ValueError("cmvn_windows: the Cmvn's CmvnStats has %d groups: give groups=" % st.groups)
+            g = _cmvn_groups("cmvn_windows", groups, B, st.groups)
+            opts = _CmvnGroupedOpts(int(cmvn.norm_vars), cmvn.pad, 0)
+            self._check(lib().clx_cmvn_grouped_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), int(layout), _np_ptr(g) if g is not None else None,
+                                                       st.groups, st._acc.data_ptr(), st._shift_scale().data_ptr(), C.byref(opts), handle))
+            return data
         if cmvn.rows is not None:
             if out is not None:
                 raise ValueError("cmvn_windows: a global Cmvn works in place: out must be None")
@@ -2333,7 +2354,7 @@ def _cmvn_flag(v, what):
 
 class Cmvn:
     """What Context.cmvn_windows and read_mel(..., cmvn=) do to every window: cepstral mean and variance normalisation whose
-    statistics are not the window's own (that one is Norm).  A plain value: it owns nothing on the device.  Two kinds:
+    statistics are not the window's own (that one is Norm).  A plain value: it owns nothing on the device.  Three kinds:
 
     global     a fixed float32 shift and scale per row: y = (x + shift[r]) * scale[r], two float32 operations, bit for bit what
                numpy or torch give for that expression (clx_cmvn_global_windows; in place).  global_(shift, scale),
@@ -2344,6 +2365,11 @@ class Cmvn:
                (not center) the cell's own frame: Kaldi's apply-cmvn-sliding as this project reads it (clx_cmvn_sliding_windows; out
                of place).  sliding(window, min_window, center, norm_vars) builds one, xvector() is the x-vector recipes'
                sliding(300, 100, True, False).  .rows is None.
+    grouped    a shift and scale per row and GROUP of windows (speaker), solved on the device from a CmvnStats accumulator each
+               time it is applied: Kaldi's apply-cmvn --utt2spk (clx_cmvn_grouped_windows; in place).  grouped(stats) builds one;
+               it holds a reference to the CmvnStats (the one kind that does not stand alone), .rows is the stats' rows, and
+               cmvn_windows / read_mel take the windows' groups beside it.  With one group it gives the words of
+               stats.cmvn() applied as a global one.
 
     Frames behind a window's valid ones become `pad`.  ValueError for a shift or scale that is not 1..8192 finite float32 numbers,
     for vectors of different lengths, a std that is not above 0, a stats matrix that is not [2][rows + 1] or whose count is not
@@ -2351,6 +2377,7 @@ class Cmvn:
 
     def __init__(self, shift=None, scale=None, window=None, min_window=None, center=False, norm_vars=False, pad=0.0):
         self.pad = _cmvn_pad(pad)
+        self._stats = None
         if (shift is None) != (scale is None) or (shift is None) == (window is None):
             raise ValueError("Cmvn: give shift and scale (a global one) or window (a sliding one); see global_() and sliding()")
         if shift is not None:
@@ -2408,6 +2435,21 @@ class Cmvn:
         return cls(window=window, min_window=min_window, center=center, norm_vars=norm_vars, pad=pad)
 
     @classmethod
+    def grouped(cls, stats, norm_vars=True, pad=0.0):
+        """Every window by the accumulator of its group: shift = -mean and scale = 1 / sqrt(var) (1 without norm_vars) of group g
+        of `stats` (an open CmvnStats), solved on the device when the Cmvn is applied, from what the accumulator holds then."""
+        if not isinstance(stats, CmvnStats) or stats._acc is None:
+            raise ValueError("Cmvn: grouped() needs an open CmvnStats, not %r" % (stats,))
+        self = cls.__new__(cls)
+        self.pad = _cmvn_pad(pad)
+        self._stats = stats
+        self._shift = self._scale = None
+        self.rows = stats.rows
+        self.window = self.min_window = None
+        self.center, self.norm_vars = False, _cmvn_flag(norm_vars, "norm_vars")
+        return self
+
+    @classmethod
     def xvector(cls, pad=0.0):
         """The x-vector / speaker-verification recipes' --cmn-window=300 --center=true --norm-vars=false."""
         return cls.sliding(300, 100, True, False, pad)
@@ -2424,11 +2466,15 @@ class Cmvn:
         return _CmvnSlidingOpts(self.window, self.min_window, int(self.center), int(self.norm_vars), self.pad, 0)
 
     def _key(self):
+        if self._stats is not None:
+            return ("grouped", id(self._stats), self.norm_vars, self.pad)
         if self.rows is not None:
             return ("global", self._shift.tobytes(), self._scale.tobytes(), self.pad)
         return ("sliding", self.window, self.min_window, self.center, self.norm_vars, self.pad)
 
     def __repr__(self):
+        if self._stats is not None:
+            return "Cmvn.grouped(<%d rows, %d groups>, norm_vars=%r, pad=%r)" % (self.rows, self._stats.groups, self.norm_vars, self.pad)
         if self.rows is not None:
             return "Cmvn.global_(<%d rows>, pad=%r)" % (self.rows, self.pad)
         return "Cmvn.sliding(window=%d, min_window=%d, center=%r, norm_vars=%r, pad=%r)" % (self.window, self.min_window, self.center,
@@ -2439,6 +2485,139 @@ class Cmvn:
 
     def __hash__(self):
         return hash(self._key())
+
+
+CMVN_MAX_GROUPS = 65536
+
+
+class _CmvnStatsOpts(C.Structure):       # clx_cmvn_stats_opts
+    _fields_ = [("accumulate", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _CmvnGroupedOpts(C.Structure):     # clx_cmvn_grouped_opts
+    _fields_ = [("norm_vars", C.c_uint32), ("pad", C.c_float), ("reserved", C.c_uint32)]
+
+
+def _cmvn_groups(who, groups, B, n_groups):
+    """`groups` as the int32 array the C side is given (None: NULL, every window group 0): B whole numbers in -1..n_groups - 1."""
+    if groups is None:
+        return None
+    try:
+        a = np.asarray(groups.cpu() if hasattr(groups, "cpu") else groups)
+    except Exception:
+        a = None
+    if a is None or a.ndim != 1 or a.dtype.kind not in "iu" or a.size != B:
+        raise ValueError("%s: groups must be %d whole numbers, one per window" % (who, B))
+    a = a.astype(np.int64)
+    if a.size and (a.min() < -1 or a.max() >= n_groups):
+        raise ValueError("%s: groups must lie in -1..%d" % (who, n_groups - 1))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class CmvnStats:
+    """Kaldi's CMVN accumulator on the device (compute-cmvn-stats): for each of `groups` groups (speakers; 1: a corpus) the sums
+    and the sums of squares of every feature row over the live frames it has been given, and their number, as float64
+    [groups][2][rows + 1] in Kaldi's layout (clx_cmvn_stats_windows has the definition and the order of the sums: the same calls
+    leave the same words).  It owns the accumulator, zeroed at creation, and the shift / scale buffer a Cmvn.grouped(self) solves
+    into.  accumulate() and reset() queue on a stream and do not wait; two calls on one CmvnStats must be ordered by the caller (one
+    stream, or events).  numpy() is the one method that waits."""
+
+    def __init__(self, ctx, rows, groups=1):
+        import torch
+        if not isinstance(ctx, Context) or ctx._h is None:
+            raise ValueError("CmvnStats: ctx must be an open Context")
+        self.ctx = ctx
+        self.rows = _cmvn_whole(rows, 1, CMVN_MAX_ROWS, "rows")
+        self.groups = _cmvn_whole(groups, 1, CMVN_MAX_GROUPS, "groups")
+        dev = torch.device("cuda", int(ctx.device))
+        self._acc = torch.zeros((self.groups, 2, self.rows + 1), dtype=torch.float64, device=dev)
+        self._ss = None                                      # [groups][2][rows] float32, made by the first grouped apply
+        torch.cuda.current_stream(dev).synchronize()         # (the zeros stand before any stream's first call)
+
+    def _open(self, who):
+        if self._acc is None:
+            raise ValueError("CmvnStats: %s on a closed CmvnStats" % who)
+
+    def _shift_scale(self):
+        if self._ss is None:
+            import torch
+            self._ss = torch.empty((self.groups, 2, self.rows), dtype=torch.float32, device=self._acc.device)
+        return self._ss
+
+    def accumulate(self, data, valid, layout, groups=None, stream=None):
+        """clx_cmvn_stats_windows, accumulating: adds the first valid[k] frames of every window of the dense float32 batch `data`
+        -- [B, rows, T] (WINDOW_CT) or [B, T, rows] (WINDOW_TC), a CUDA tensor or a (pointer, B, rows, T) tuple -- to the
+        accumulator of group groups[k] (None: group 0; -1: the window takes no part).  `data` is only read.  Asynchronous on
+        `stream` as gather_windows is.  Returns self."""
+        self._open("accumulate()")
+        d_ptr, B, rows, T, valid, handle = self.ctx._feature_batch("CmvnStats.accumulate", data, valid, layout, stream)
+        if rows != self.rows:
+            raise ValueError("CmvnStats.accumulate: the CmvnStats has %d rows, the batch %d" % (self.rows, rows))
+        g = _cmvn_groups("CmvnStats.accumulate", groups, B, self.groups)
+        opts = _CmvnStatsOpts(1, 0)
+        self.ctx._check(lib().clx_cmvn_stats_windows(self.ctx._h, d_ptr, B, rows, T, _np_ptr(valid), int(layout), _np_ptr(g) if g is not None else None,
+                                                     self.groups, self._acc.data_ptr(), C.byref(opts), handle))
+        return self
+
+    def reset(self, stream=None):
+        """Zeroes the accumulator: clx_cmvn_stats_windows over no window with accumulate = 0, queued on `stream` and not waited for.
+        stream=None is torch's current stream of the accumulator's device -- the stream accumulate() and read_mel(stats=) take for
+        a tensor when they are given none, so reset() followed by either, with no stream named, is ordered.  (As with every call
+        here, torch's DEFAULT stream stands for the context's own stream.)"""
+        self._open("reset()")
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self._acc.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        opts = _CmvnStatsOpts(0, 0)
+        self.ctx._check(lib().clx_cmvn_stats_windows(self.ctx._h, None, 0, self.rows, 0, None, WINDOW_CT, None, self.groups, self._acc.data_ptr(),
+                                                     C.byref(opts), C.c_void_p(handle) if handle else None))
+        return self
+
+    def numpy(self):
+        """The accumulator on the host, float64 [2, rows + 1] for one group, else [groups, 2, rows + 1].  WAITS for the device."""
+        self._open("numpy()")
+        import torch
+        torch.cuda.synchronize(self._acc.device)
+        a = self._acc.cpu().numpy()
+        return a[0].copy() if self.groups == 1 else a
+
+    def add_(self, array):
+        """Adds another accumulator of the same shape (another rank's numpy(), a Kaldi stats file) on the host and uploads the sum.
+        Waits, as numpy() does.  Returns self."""
+        self._open("add_()")
+        import torch
+        mine = self.numpy()
+        try:
+            a = np.asarray(array, dtype=np.float64)
+        except Exception:
+            a = None
+        if a is None or a.shape != mine.shape:
+            raise ValueError("CmvnStats.add_: the array must be float64 of shape %r" % (mine.shape,))
+        total = (mine + a).reshape(self.groups, 2, self.rows + 1)
+        self._acc.copy_(torch.from_numpy(np.ascontiguousarray(total)))
+        torch.cuda.synchronize(self._acc.device)
+        return self
+
+    def cmvn(self, norm_vars=True, pad=0.0):
+        """Cmvn.from_kaldi_stats(self.numpy(), ...): a global Cmvn, a plain value that no longer reads this object.  One group only."""
+        if self.groups != 1:
+            raise ValueError("CmvnStats.cmvn: needs groups == 1; Cmvn.grouped(stats) is the one for %d groups" % self.groups)
+        return Cmvn.from_kaldi_stats(self.numpy(), norm_vars=norm_vars, pad=pad)
+
+    def as_wenet(self):
+        """WeNet's global_cmvn statistics: {"mean_stat": the sums, "var_stat": the sums of squares, "frame_num": the count}, as
+        lists (json.dump them).  One group only."""
+        if self.groups != 1:
+            raise ValueError("CmvnStats.as_wenet: needs groups == 1")
+        a = self.numpy()
+        return {"mean_stat": a[0, :-1].tolist(), "var_stat": a[1, :-1].tolist(), "frame_num": int(a[0, -1])}
+
+    def close(self):
+        self._acc = self._ss = None
+
+    def __repr__(self):
+        return "CmvnStats(<%d rows, %d groups>%s)" % (self.rows, self.groups, "" if self._acc is not None else ", closed")
 
 
 # ---- energy VAD and frame selection ------------------------------------------------------------------------------------------------
@@ -3112,7 +3291,7 @@ class StreamSet:
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
 
 
-    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None, cmvn=None, vad=None, return_vad=False):
+    def read_mel(self, stream_ids, starts, n_frames, spec, layout="ct", length=None, normalize=None, add=None, reverb=None, augment=None, splice=None, cmvn=None, vad=None, return_vad=False, stats=None, groups=None):
         """A batch of feature windows: for window k, n_frames frames of `spec` (a MelSpec of this set's context) over the samples from
         starts[k] on of stream stream_ids[k], counted at spec.sample_rate and brought to one channel.  Exactly
         read(stream_ids, starts, L, "ct", sample_rate=spec.sample_rate, channels=1) -- its refusals, its frames decoded -- followed by
@@ -3183,7 +3362,17 @@ class StreamSet:
         select=False the features and valid_frames are untouched and nothing waits.  return_vad=True appends the mask (uint8
         [B, n_frames] on the GPU) to the return value: its time axis is the one before the selection, and its bytes from
         valid_frames on are 0.  ValueError for a vad that is not a Vad, a vad.row that is not below the row count behind splice=,
-        and return_vad=True without vad=.  vad=None is the call without the argument."""
+        and return_vad=True without vad=.  vad=None is the call without the argument.
+
+        With stats=CmvnStats the batch is also ADDED to that accumulator (compute-cmvn-stats): one clx_cmvn_stats_windows call
+        exactly where cmvn= would read the batch -- behind splice= and the VAD decision, in front of normalize= / cmvn=, over
+        valid_frames' frames and before any selection.  The tensors returned do not change, and nothing waits: a whole corpus
+        pass can be queued and stats.numpy() asked at the end.  groups= is B whole numbers, window k's group (speaker) in
+        0..groups - 1 or -1 for a window that takes no part: shared by stats= and a grouped cmvn= (Cmvn.grouped(other_stats):
+        apply-cmvn --utt2spk).  ValueError for a stats that is not an open CmvnStats of the set's context, rows that are not the
+        call's row count behind splice=, groups of the wrong length or range, groups= with neither consumer, a grouped cmvn=
+        without groups= when its stats have more than one group, and stats= being the object the call's grouped cmvn= reads:
+        accumulate in one pass, apply in the next.  stats=None, groups=None is the call without the arguments."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read_mel: normalize must be a Norm or None, not %r" % (normalize,))
         if augment is not None and not isinstance(augment, (SpecAugment, SpecAugmentPlan)):
@@ -3202,11 +3391,28 @@ class StreamSet:
             raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
         if reverb is not None and not isinstance(reverb, Reverb):
             raise ValueError("read_mel: reverb must be a Reverb or None, not %r" % (reverb,))
+        if stats is not None and (not isinstance(stats, CmvnStats) or stats._acc is None or stats.ctx is not self.ctx):
+            raise ValueError("read_mel: stats must be an open CmvnStats of the set's context or None, not %r" % (stats,))
+        cmvn_stats = cmvn._stats if cmvn is not None else None
+        if cmvn_stats is not None and cmvn_stats._acc is None:
+            raise ValueError("read_mel: the grouped Cmvn's CmvnStats is closed")
+        if groups is not None and stats is None and cmvn_stats is None:
+            raise ValueError("read_mel: groups= needs stats= or a grouped cmvn=")
+        if stats is not None and stats is cmvn_stats:
+            raise ValueError("read_mel: stats= is the CmvnStats the grouped cmvn= reads: accumulate in one pass, apply in the next")
+        if groups is None and cmvn_stats is not None and cmvn_stats.groups > 1:
+            raise ValueError("read_mel: the grouped Cmvn's CmvnStats has %d groups: give groups=" % cmvn_stats.groups)
         import torch
         if layout not in _LAYOUTS:
             raise ValueError("read_mel: layout must be 'tc' or 'ct', not %r" % (layout,))
         if not isinstance(spec, MelSpec) or spec._h is None or spec.ctx is not self.ctx:
             raise ValueError("read_mel: spec must be an open MelSpec of the set's context")
+        if stats is not None and stats.rows != (spec.n_out if splice is None else splice.n_out(spec.n_out)):
+            raise ValueError("read_mel: the CmvnStats has %d rows, the features %d" % (stats.rows, spec.n_out if splice is None else splice.n_out(spec.n_out)))
+        if groups is not None:
+            for who in (stats, cmvn_stats):
+                if who is not None:
+                    _cmvn_groups("read_mel", groups, int(np.asarray(stream_ids).size), who.groups)
         if cmvn is not None and cmvn.rows is not None and cmvn.rows != (spec.n_out if splice is None else splice.n_out(spec.n_out)):
             raise ValueError("read_mel: the Cmvn has %d rows, the features %d" % (cmvn.rows, spec.n_out if splice is None else splice.n_out(spec.n_out)))
         if vad is not None and vad.row >= (spec.n_out if splice is None else splice.n_out(spec.n_out)):
@@ -3241,10 +3447,12 @@ class StreamSet:
         mask = None
         if vad is not None:                                  # (queued in front of the normaliser, which may work in place)
             mask = self.ctx.vad_windows(out, vf, _LAYOUTS[layout], vad)
+        if stats is not None:                                # (where cmvn= reads the batch; nothing of it is written)
+            stats.accumulate(out, vf, _LAYOUTS[layout], groups)
         if normalize is not None:
             self.ctx.norm_windows(out, vf, _LAYOUTS[layout], normalize)
         if cmvn is not None:
-            out = self.ctx.cmvn_windows(out, vf, _LAYOUTS[layout], cmvn)
+            out = self.ctx.cmvn_windows(out, vf, _LAYOUTS[layout], cmvn, groups=groups if cmvn_stats is not None else None)
         if vad is not None and vad.select:
             out, vf = self.ctx.select_windows(out, vf, mask, _LAYOUTS[layout], vad.pad)
         if augment is not None:

@@ -20,6 +20,7 @@
 #include "clx_specaug.hip"
 #include "clx_splice.hip"
 #include "clx_cmvn.hip"
+#include "clx_cmvn_stats.hip"           // (behind clx_norm.hip and clx_cmvn.hip: the chunk sums are the former's, the apply the latter's)
 #include "clx_vad.hip"                  // (behind clx_norm.hip: the energy sum is that file's)
 
 #include <algorithm>
@@ -346,6 +347,11 @@ struct clx_ctx {
     // device only, count per window, the tile counts and the tile bases, and in the staging behind V the counts on their way to
     // the host.  Beside it the decision's partial sums
     clx_call_scratch vad { "vad", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    // clx_cmvn_stats_windows and clx_cmvn_grouped_windows (one set for both; in 32-bit words): V and the group per window, then the
+    // accumulating call's groups and their windows (CSR).  Beside it that call's partial sums, and on the host the counting sort's
+    // work array (zeros between calls)
+    clx_call_scratch cmvns { "cmvn_stats", 64, sizeof(uint32_t), sizeof(uint32_t) };
+    std::vector<uint32_t> cmvns_slot;
 };
 
 struct clx_mel_spec {
@@ -564,6 +570,7 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     ctx->sp.release();
     ctx->cmvn.release();
     ctx->vad.release();
+    ctx->cmvns.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -2081,6 +2088,72 @@ extern "C" int clx_cmvn_sliding_windows(clx_ctx* ctx, const void* d_in, void* d_
 
 extern "C" int clx_cmvn_from_stats(const double* stats, uint32_t rows, uint32_t norm_vars, float* shift, float* scale) {
     return clx_cmvn_from_stats_build(stats, rows, norm_vars, shift, scale) ? CLX_API_ERROR : CLX_OK;
+}
+
+extern "C" int clx_cmvn_stats_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                      uint32_t layout, const int32_t* group, uint32_t n_groups, void* d_stats, const clx_cmvn_stats_opts* opts,
+                                      void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_cmvn_stats_plan pl;
+    const char* why = clx_cmvn_stats_check(d_data, n_windows, rows, T, valid, layout, group, n_groups, d_stats, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (!pl.launch && opts->accumulate) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    if (!pl.launch) {                                          // a reset without windows: the zeros alone
+        HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, (size_t)pl.stats_bytes, stream));
+        return CLX_OK;
+    }
+    const size_t words = (size_t)pl.table_words;
+    clx_call_scratch& s = ctx->cmvns;
+    if (s.begin(ctx, stream, words, (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;
+    const uint32_t present = clx_cmvn_stats_fill_table((uint32_t*)s.h, n_windows, valid, group, n_groups, true, ctx->cmvns_slot);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    if (!opts->accumulate) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, (size_t)pl.stats_bytes, stream));
+    if (present) {
+        if (pl.tc)
+            hipLaunchKernelGGL(clx_k_cmvn_stats_sum_tc, dim3(pl.sum_blocks), dim3(clx_cmvn_stats::kThreads), 0, stream, (const float*)d_data,
+                               (const uint32_t*)s.d, (double*)s.part.p, (uint32_t)n_windows, rows, T, pl.n_chunks, pl.n_rgroups);
+        else
+            hipLaunchKernelGGL(clx_k_cmvn_stats_sum, dim3(pl.sum_blocks), dim3(clx_cmvn_stats::kThreads), 0, stream, (const float*)d_data,
+                               (const uint32_t*)s.d, (double*)s.part.p, (uint32_t)n_windows, rows, T, pl.n_chunks,
+                               (uint64_t)n_windows * rows * pl.n_chunks);
+        HIP_TRY(ctx, hipGetLastError());
+        const uint64_t lanes = (uint64_t)present * 2u * (rows + 1u);
+        hipLaunchKernelGGL(clx_k_cmvn_stats_fold, dim3((unsigned)((lanes + clx_cmvn_stats::kThreads - 1u) / clx_cmvn_stats::kThreads)),
+                           dim3(clx_cmvn_stats::kThreads), 0, stream, (const double*)s.part.p, (const uint32_t*)s.d, (double*)d_stats,
+                           (uint32_t)n_windows, rows, pl.n_chunks, lanes);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_cmvn_grouped_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                        uint32_t layout, const int32_t* group, uint32_t n_groups, const void* d_stats, void* d_shift_scale,
+                                        const clx_cmvn_grouped_opts* opts, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_cmvn_stats_plan pl;
+    const char* why = clx_cmvn_grouped_check(d_data, n_windows, rows, T, valid, layout, group, n_groups, d_stats, d_shift_scale, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (!pl.launch) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    const size_t words = (size_t)pl.table_words;
+    clx_call_scratch& s = ctx->cmvns;
+    if (s.begin(ctx, stream, words, 0) != CLX_OK) return CLX_API_ERROR;    // (no partial sums of its own: reserved with need 0)
+    (void)clx_cmvn_stats_fill_table((uint32_t*)s.h, n_windows, valid, group, n_groups, false, ctx->cmvns_slot);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d, s.h, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    hipLaunchKernelGGL(clx_k_cmvn_stats_solve, dim3(pl.solve_blocks), dim3(clx_cmvn_stats::kThreads), 0, stream, (const double*)d_stats,
+                       (float*)d_shift_scale, n_groups, rows, opts->norm_vars);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_cmvn_grouped, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_cmvn_stats::kThreads), 0, stream, (float*)d_data,
+                       (const uint32_t*)s.d, (const float*)d_shift_scale, (uint32_t)n_windows, rows, T, opts->pad, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
 }
 
 extern "C" int clx_vad_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid, uint32_t layout,

@@ -955,8 +955,8 @@ int  clx_splice_deltas(uint32_t order, uint32_t window, clx_splice_block* blocks
  * valid is staged as above (the table is V per window).  CLX_API_ERROR, each with a text of its own, for opts == NULL, reserved
  * bits, a pad that is not finite, an unknown layout, rows outside 1..8192, T above 2^31 - 1, window outside 1..1024, center or
  * norm_vars above 1, with center == 0 a min_window outside 1..window, a null d_in, d_out or valid, d_out == d_in, a valid[k] > T
- * and more than 2^31 - 1 tiles.  n_windows == 0 or T == 0 succeeds and launches nothing.  Not here: windows above 1024 frames,
- * accumulating the statistics of a corpus.  (Kaldi's VAD is clx_vad_windows below.)
+ * and more than 2^31 - 1 tiles.  n_windows == 0 or T == 0 succeeds and launches nothing.  Not here: windows above 1024 frames.
+ * (Accumulating the statistics of a corpus is clx_cmvn_stats_windows, Kaldi's VAD is clx_vad_windows, both below.)
  *
  * clx_cmvn_from_stats (host only, no context) turns Kaldi's CMVN accumulator into shift and scale: stats is [2][rows + 1] doubles,
  * row 0 the sums and the count, row 1 the sums of squares (its last entry unused).  mean = sum / count,
@@ -971,6 +971,79 @@ int  clx_cmvn_global_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint3
 int  clx_cmvn_sliding_windows(clx_ctx* ctx, const void* d_in, void* d_out, size_t n_windows, uint32_t rows, uint32_t T,
                               const uint32_t* valid, uint32_t layout, const clx_cmvn_sliding_opts* opts, void* stream);
 int  clx_cmvn_from_stats(const double* stats, uint32_t rows, uint32_t norm_vars, float* shift, float* scale);
+/* Kaldi's CMVN accumulator on the device (compute-cmvn-stats, per corpus or per speaker), and the normalisation of every window by
+ * the accumulator of its group (apply-cmvn --utt2spk).  d_data is a dense float32 feature batch, [n_windows][rows][T]
+ * (CLX_WINDOW_CT) or [n_windows][T][rows] (CLX_WINDOW_TC), rows in 1..8192, window k with V = valid[k] <= T live frames:
+ * clx_cmvn_global_windows' shape and limits.  group is n_windows int32 on the host: group[k] in 0..n_groups - 1 is the group
+ * (speaker) of window k, -1 says the window takes no part, group == NULL says every window is group 0.  n_groups is 1..65536.
+ * d_stats is the accumulator, device memory the caller owns, 8-byte aligned: [n_groups][2][rows + 1] doubles in Kaldi's layout --
+ * row 0 the sums of the group's live cells per feature row, with the number of frames in column `rows`; row 1 the sums of their
+ * squares, with column `rows` unused (0 behind a reset, otherwise untouched).  One group's [2][rows + 1] on the host is what
+ * clx_cmvn_from_stats and a Kaldi stats file hold.
+ *
+ * The accumulation, clx_cmvn_stats_windows: d_data is only read.
+ *
+ *   options    accumulate (0: the accumulator is zeroed first, all n_groups groups of it; 1: the call adds to what it holds).
+ *   ORDER      per window k, feature row r and chunk c of 4096 frames the call forms S_c, the double sum of (double)x[t], and
+ *              Q_c, the double sum of (double)x[t] * (double)x[t] (exact in double: raw squares, as Kaldi's accumulator holds
+ *              them, not deviations), over the chunk's live frames exactly as clx_norm_windows forms its S_c: strand i of 64 adds
+ *              the frames t = i mod 64 ascending from +0.0, the strands are folded by xor 32, 16, 8, 4, 2, 1 (strand i takes
+ *              strand i ^ d), every addition a double addition rounded once.  W[k][r] is the S_c of the window's live chunks
+ *              added ascending from +0.0 (a window with V = 0: +0.0), likewise for Q.  Then, per group g and word of it,
+ *              acc = accumulate ? the word : +0.0, and acc += W[k] for the windows k with group[k] == g in ascending k; the count
+ *              column adds (double)valid[k] the same way.  The order is a function of (valid, group) alone, never of the
+ *              layout or the grid, and nothing is added atomically: the same calls leave the same words.
+ *   absent     a group without a window in this call keeps its words (accumulate) or is zeros (reset).  A group whose windows
+ *              all have V = 0 adds +0.0 to its words.
+ *   reads      no cell with t >= V is read, whatever it holds, and no cell of a window with group -1.  Cells that are not finite
+ *              give what IEEE gives in their group, row and sum, and nothing elsewhere.
+ *   layouts    CT and TC of the same data give the same words.
+ *   plan       a memset of the accumulator (reset only), then two launches: clx_k_cmvn_stats_sum (CT, and TC with one row: a wave
+ *              is one chunk of one row, no LDS) or clx_k_cmvn_stats_sum_tc (TC: clx_norm's tile of 64 frames x 16 rows through
+ *              4 352 bytes of LDS) makes one pass over the data and leaves S_c and Q_c in a per-call table of doubles
+ *              [n_windows][rows][2][chunks]; clx_k_cmvn_stats_fold, one lane a (group with a window, column, S | Q), folds them
+ *              into the accumulator along the host's list of each group's windows (a stable counting sort, CSR, part of the
+ *              call's staged table).
+ *
+ * Two calls that accumulate into one d_stats read and write the same words: the caller has to order them, by queueing them on
+ * one stream or by an event between their streams.  (The per-call tables are the context's and are handed from call to call as
+ * every window call's are; d_stats is the caller's and is not.)
+ *
+ * The normalisation, clx_cmvn_grouped_windows, in place: d_shift_scale is device memory the caller owns, [n_groups][2][rows]
+ * floats (a group's shifts, then its scales), written by the call and only meaningful to it: nothing is allocated per call.
+ *
+ *   options    norm_vars (0 or 1), pad.
+ *   solve      per group and row, clx_cmvn_from_stats' arithmetic on the device, word for word: in double, nothing fused,
+ *              mean = sum / count, var = max(sumsq / count - mean * mean, 1e-20), shift = (float)(-mean),
+ *              scale = norm_vars ? (float)(1 / sqrt(var)) : 1 (a correctly rounded division and square root, each result rounded
+ *              once to float32).  A group whose count is not above 0 gets shift +0.0 and scale 1.0f (its cells come out as x + 0);
+ *              statistics that are not finite give what IEEE gives, in that group only -- where clx_cmvn_from_stats refuses.
+ *   live       for t < V and g = group[k] >= 0, y = fl32(fl32(x + shift[g][r]) * scale[g][r]), clx_cmvn_global_windows' two
+ *              float32 operations: with one group, the words of clx_cmvn_global_windows given clx_cmvn_from_stats' vectors.  A
+ *              window with group -1 keeps its live cells.
+ *   padding    every cell with t >= V becomes the word of opts->pad, in a window of group -1 too.
+ *   reads      no cell with t >= V is read.  d_stats is only read.
+ *   layouts    CT and TC of the same data give the same words.
+ *   plan       two launches: clx_k_cmvn_stats_solve, one lane a (group, row), over all n_groups groups; clx_k_cmvn_grouped,
+ *              clx_k_cmvn_global's tiling (1024 16-byte vectors a block, 16-byte accesses where a vector lies whole inside the
+ *              window and its live cells), shift and scale read from d_shift_scale.  No LDS.
+ *
+ * valid and group are staged before either call returns (one pinned table a call, as clx_cmvn_global_windows stages its arrays), so
+ * the calls are asynchronous on `stream` (NULL: the context's), return without waiting for the device, and the arrays may be reused
+ * at once.  n_windows == 0 or T == 0 succeeds and launches nothing -- except that clx_cmvn_stats_windows with accumulate == 0 still
+ * zeroes the accumulator (that is how an accumulator is reset on a stream).  CLX_API_ERROR, each with a clx_last_error text of its
+ * own, for opts == NULL, reserved bits, accumulate or norm_vars above 1, a pad that is not finite, an unknown layout, rows outside
+ * 1..8192, T above 2^31 - 1, n_groups outside 1..65536, a null d_stats, a d_stats that is not 8-byte aligned, a null or misaligned
+ * d_shift_scale, a null d_data or valid, a valid[k] > T, a group[k] outside -1..n_groups - 1 and more than 2^31 - 1 blocks in a
+ * launch. */
+typedef struct { uint32_t accumulate; uint32_t reserved; } clx_cmvn_stats_opts;
+typedef struct { uint32_t norm_vars; float pad; uint32_t reserved; } clx_cmvn_grouped_opts;
+int  clx_cmvn_stats_windows(clx_ctx* ctx, const void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                            uint32_t layout, const int32_t* group, uint32_t n_groups, void* d_stats, const clx_cmvn_stats_opts* opts,
+                            void* stream);
+int  clx_cmvn_grouped_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                              uint32_t layout, const int32_t* group, uint32_t n_groups, const void* d_stats, void* d_shift_scale,
+                              const clx_cmvn_grouped_opts* opts, void* stream);
 /* Kaldi's energy VAD over one row of a dense float32 feature batch on the device (compute-vad), and the selection of the frames a
  * byte mask names (select-voiced-frames, or any other mask: a neural VAD's).  d_data is [n_windows][rows][n_frames] (CLX_WINDOW_CT)
  * or [n_windows][n_frames][rows] (CLX_WINDOW_TC), rows 1..8192; valid[k] <= n_frames is window k's live frames V.
