@@ -89,6 +89,8 @@ FRAME_RESULT_DTYPE = np.dtype([("status", "<i4"), ("msg", "<u4"), ("end_bit", "<
 FRAME_HEADER_DTYPE = np.dtype([("time", "<u8"), ("sample_rate", "<u4"), ("frame_or_sample_lo", "<u4"),
                                ("block_size", "<u2"), ("header_bytes", "<u2"), ("n_channels", "u1"),
                                ("channel_assignment", "u1"), ("bps", "u1"), ("variable_blocking", "u1")])
+ADDN_TERM_DTYPE = np.dtype([("batch", "<i4"), ("index", "<i4"), ("offset", "<u4"), ("loop", "<u4"), ("snr_db", "<f4")])   # clx_addn_term
+ADDN_MAX_TERMS, ADDN_MAX_BATCHES = 16, 8
 assert FRAME_DESC_DTYPE.itemsize == C.sizeof(FrameDesc) == 24
 assert FRAME_RESULT_DTYPE.itemsize == C.sizeof(FrameResult) == 16
 assert FRAME_HEADER_DTYPE.itemsize == C.sizeof(FrameHeader) == 24
@@ -102,7 +104,7 @@ EXPORTS = [
     "clx_reader_streaminfo", "clx_reader_next_block", "clx_reader_close", "clx_index_frames", "clx_index_frames_device",
     "clx_read_metadata_block", "clx_read_metadata_block_with_header", "clx_describe_packets", "clx_md5_streams", "clx_index_streams_device", "clx_gather_windows",
     "clx_resample_windows", "clx_mix_windows", "clx_mel_create", "clx_mel_create_ex", "clx_mel_create_framed", "clx_mel_create_cepstral", "clx_mel_create_reflected", "clx_mel_destroy", "clx_mel_windows",
-    "clx_norm_windows", "clx_add_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
+    "clx_norm_windows", "clx_add_windows", "clx_addn_windows", "clx_reverb_windows", "clx_reverb_windows_fft", "clx_specaug_windows",
     "clx_splice_windows", "clx_splice_deltas", "clx_cmvn_global_windows", "clx_cmvn_sliding_windows", "clx_cmvn_from_stats",
     "clx_vad_windows", "clx_select_windows", "clx_cmvn_stats_windows", "clx_cmvn_grouped_windows",
 ]
@@ -110,7 +112,7 @@ EXPORTS = [
 
 def build(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_cmvn_stats.hip", "clx_vad.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
+    srcs = [os.path.join(_CSRC, f) for f in ("clx_api.hip", "clx_kernels.hip", "clx_lanes.hip", "clx_lean.hip", "clx_md5.hip", "clx_index.hip", "clx_window.hip", "clx_resample.hip", "clx_mix.hip", "clx_mel.hip", "clx_norm.hip", "clx_add.hip", "clx_addn.hip", "clx_reverb.hip", "clx_reverb_fft.hip", "clx_specaug.hip", "clx_splice.hip", "clx_cmvn.hip", "clx_cmvn_stats.hip", "clx_vad.hip", "clx_device.h", "clx_crct.h", "clx_plan.h",
                                             os.path.join("intrin", "clx_intrin.h"), os.path.join("intrin", "clx_k2_dot2.h"), os.path.join("host", "claxon.hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "claxon_hip.h"))
     if (not force and os.path.exists(LIB_PATH)
@@ -199,6 +201,7 @@ def lib():
     L.clx_mel_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.clx_norm_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.clx_add_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.clx_addn_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.clx_reverb_windows.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.clx_reverb_windows_fft.argtypes = L.clx_reverb_windows.argtypes
     L.clx_specaug_windows.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
@@ -846,6 +849,71 @@ class Context:
         g_ptr = gains.data_ptr() if hasattr(gains, "data_ptr") else (int(gains) if gains else None)
         self._check(lib().clx_add_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), n_ptr, N, _np_ptr(noise_valid), _np_ptr(noise_index),
                                           _np_ptr(snr), int(layout), None, g_ptr, C.c_void_p(handle) if handle else None))
+        return data
+
+    def addn_windows(self, data, valid, noises, noise_valid, term_first, batch, index, offset, loop, snr_db, layout, gains=None, stream=None):
+        """clx_addn_windows: several placed or looped noises added in place to the dense float32 batch `data` ([B, rows, T] for
+        WINDOW_CT, [B, T, rows] for WINDOW_TC, rows 1..8) in one pass, each at its own signal-to-noise ratio against the signal as it
+        arrives (claxon_hip.h has the definition and the order of the sums).  `noises` is a sequence of up to 8 noise batches with
+        data's layout, rows and T; noise_valid is one array, concatenated over the batches.  Window k has the terms
+        term_first[k] .. term_first[k + 1] - 1 (at most 16); term m adds noise window index[m] (-1: nothing) of batch batch[m] from
+        window sample offset[m] on, looped over the rest of the window where loop[m] is 1, at snr_db[m].  batch, offset, loop and
+        snr_db are scalars or one value per term.  Padding and the cells no term covers keep their words; no noise is written.
+        `gains`, if given, is an [M] float32 tensor that receives every term's gain.  `data`, the noises and `gains` are CUDA
+        float32 tensors, or `data` is a (pointer, B, rows, T) tuple, each noise a (pointer, N) pair and `gains` a pointer.
+        Asynchronous on `stream` as gather_windows is.  Returns `data`."""
+        tc = int(layout) == WINDOW_TC
+        if hasattr(data, "data_ptr"):
+            if data.dim() != 3 or not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("addn_windows: data must be a contiguous float32 [B, rows, T] or [B, T, rows] tensor")
+            d_ptr, B = data.data_ptr(), int(data.shape[0])
+            rows, T = (int(data.shape[2]), int(data.shape[1])) if tc else (int(data.shape[1]), int(data.shape[2]))
+        else:
+            d_ptr, B, rows, T = (int(data[0]) if data[0] else None), int(data[1]), int(data[2]), int(data[3])
+        noises = list(noises)
+        ptrs, counts = (C.c_void_p * max(len(noises), 1))(), (C.c_size_t * max(len(noises), 1))()
+        for b, noise in enumerate(noises):
+            if hasattr(noise, "data_ptr"):
+                if noise.dim() != 3 or not noise.is_contiguous() or str(noise.dtype) != "torch.float32" \
+                        or tuple(noise.shape[1:]) != ((T, rows) if tc else (rows, T)):
+                    raise ValueError("addn_windows: a noise batch must be a contiguous float32 [N, rows, T] or [N, T, rows] tensor with data's rows and T")
+                ptrs[b], counts[b] = noise.data_ptr() or None, int(noise.shape[0])
+            else:
+                ptrs[b], counts[b] = (int(noise[0]) if noise[0] else None), int(noise[1])
+        valid = np.ascontiguousarray(valid, dtype=np.uint32).reshape(-1)
+        noise_valid = np.ascontiguousarray(noise_valid, dtype=np.uint32).reshape(-1)
+        term_first = np.ascontiguousarray(term_first, dtype=np.uint32).reshape(-1)
+        if valid.size != B:
+            raise ValueError("addn_windows: valid has %d entries for %d windows" % (valid.size, B))
+        if term_first.size != B + 1:
+            raise ValueError("addn_windows: term_first has %d entries for %d windows" % (term_first.size, B))
+        if noise_valid.size != sum(counts[:len(noises)]):
+            raise ValueError("addn_windows: noise_valid has %d entries for %d windows" % (noise_valid.size, sum(counts[:len(noises)])))
+        M = int(term_first[-1])
+        terms = np.zeros(M, dtype=ADDN_TERM_DTYPE)
+        for name, a, dt in (("batch", batch, np.int32), ("index", index, np.int32), ("offset", offset, np.uint32), ("loop", loop, np.uint32),
+                            ("snr_db", snr_db, np.float32)):
+            wide = np.asarray(a, dtype=np.float32 if dt is np.float32 else np.int64).reshape(-1)
+            if dt is not np.float32 and wide.size and (wide.min() < np.iinfo(dt).min or wide.max() > np.iinfo(dt).max):
+                raise ValueError("addn_windows: %s is out of range" % name)
+            if wide.size == 1 and M != 1 and name != "index":
+                wide = np.full(M, wide[0])
+            if wide.size != M:
+                raise ValueError("addn_windows: %s has %d entries for %d terms" % (name, wide.size, M))
+            terms[name] = wide.astype(dt)
+        for name, v in (("rows", rows), ("T", T), ("layout", layout)):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("addn_windows: %s is out of range" % name)
+        if hasattr(gains, "data_ptr"):
+            if gains.numel() != M or not gains.is_contiguous() or str(gains.dtype) != "torch.float32":
+                raise ValueError("addn_windows: gains must be a contiguous float32 tensor of one value per term")
+        if stream is None and hasattr(data, "data_ptr"):
+            import torch
+            stream = torch.cuda.current_stream(data.device)
+        handle = getattr(stream, "cuda_stream", stream)
+        g_ptr = gains.data_ptr() if hasattr(gains, "data_ptr") else (int(gains) if gains else None)
+        self._check(lib().clx_addn_windows(self._h, d_ptr, B, rows, T, _np_ptr(valid), ptrs, counts, len(noises), _np_ptr(noise_valid),
+                                           _np_ptr(term_first), _np_ptr(terms), int(layout), None, g_ptr, C.c_void_p(handle) if handle else None))
         return data
 
     def reverb_windows(self, data, valid, ir, ir_len, ir_index, layout, out=None, keep_power=True, gains=None, stream=None, method="direct"):
@@ -2866,9 +2934,17 @@ class Add:
     A noise stream that ends inside the window is added as far as it goes and counted over that part only; it is not repeated.
     A plain value: it owns nothing on the device.  ValueError for arrays that differ in length, an id below -1, a negative start
     and a snr_db that is NaN, -inf or beyond 200 in magnitude; the read refuses lengths that differ from its own, an id the source
-    does not have, a closed source and a source of another context."""
+    does not have, a closed source and a source of another context.
 
-    def __init__(self, stream_ids, starts, snr_db, source=None):
+    offsets (a scalar or one value per window, >= 0, in samples at the call's rate) is the window sample at which the noise enters:
+    a foreground noise dropped in along the utterance.  tile (a bool, or one per window) repeats the noise from its live end --
+    the noise window's valid length, min(what the stream has from starts[k] on, the call's length) -- over the rest of the window:
+    music or background noise looped under the whole utterance.  The gain then counts the noise over the samples it sounds on, as
+    often as they sound (clx_addn_windows, claxon_hip.h).  An Add with an offset or a tile, and every Add in a list
+    (add=[Add, ...]: babble, several foreground noises), goes through clx_addn_windows; a plain one alone goes through
+    clx_add_windows as ever.  ValueError also for a negative offset and for offsets or tile of another length."""
+
+    def __init__(self, stream_ids, starts, snr_db, source=None, offsets=0, tile=False):
         if source is not None and not isinstance(source, StreamSet):
             raise ValueError("Add: source must be a StreamSet or None, not %r" % (source,))
         self.stream_ids = np.array(stream_ids, dtype=np.int64).reshape(-1)
@@ -2887,7 +2963,25 @@ class Add:
             raise ValueError("Add: a noise window starts before its stream")
         if np.any(np.isnan(self.snr_db) | (np.isinf(self.snr_db) & (self.snr_db < 0)) | (np.isfinite(self.snr_db) & (np.abs(self.snr_db) > 200))):
             raise ValueError("Add: snr_db must be within -200 .. 200, or +inf")
+        off = np.array(offsets)
+        if off.dtype.kind not in "iu" or off.ndim > 1:
+            raise ValueError("Add: offsets must be a whole number or one per window")
+        off = off.astype(np.int64)
+        self.offsets = np.full(self.stream_ids.size, off, dtype=np.int64) if off.ndim == 0 else off
+        til = np.array(tile)
+        if til.dtype.kind != "b" or til.ndim > 1:
+            raise ValueError("Add: tile must be a bool or one per window")
+        self.tile = np.full(self.stream_ids.size, til, dtype=bool) if til.ndim == 0 else til
+        if self.offsets.size != self.stream_ids.size or self.tile.size != self.stream_ids.size:
+            raise ValueError("Add: offsets and tile must be scalars or one value per window")
+        if self.offsets.size and self.offsets.min() < 0:
+            raise ValueError("Add: an offset is negative")
         self.source = source
+
+    @property
+    def plain(self):
+        """Whether clx_add_windows can take it: every offset 0, no tile."""
+        return not (np.any(self.offsets != 0) or np.any(self.tile))
 
     def __len__(self):
         return int(self.stream_ids.size)
@@ -2914,6 +3008,17 @@ class Add:
                     raise ValueError("%s: noise stream %d has %d channels, the windows %d (window %d); channels= brings them together"
                                      % (who, s, src.channels[s], ch, k))
         return src, sel
+
+
+def _adds_of(add, who):
+    """add= as a list of Adds: None, one Add, or a list or tuple of 1..16 of them."""
+    if add is None:
+        return []
+    if isinstance(add, Add):
+        return [add]
+    if isinstance(add, (list, tuple)) and 1 <= len(add) <= ADDN_MAX_TERMS and all(isinstance(a, Add) for a in add):
+        return list(add)
+    raise ValueError("%s: add must be an Add, a list of 1..%d Adds or None, not %r" % (who, ADDN_MAX_TERMS, add))
 
 
 # ---- room impulse responses over the windows ------------------------------------------------------------------------------------
@@ -3157,8 +3262,20 @@ class StreamSet:
         noise stream that ends inside a window is added as far as it goes.  With channels=None the noise streams must have the
         windows' channel count.  return_gains=True appends the windows' gains (float32 [B] on the GPU, 0 where nothing was added) to
         the return value.  ValueError for an add that is not an Add, whose length is not this call's, that names a stream its
-        source does not have, or whose source is closed or of another context.  Tiling a short noise over a long window, several
-        Adds in one call and other gain rules are not offered.
+        source does not have, or whose source is closed or of another context.  Other gain rules are not offered.
+
+        add= also takes a list of 1..16 Adds -- babble, several foreground noises, music under speech and a noise on top -- and
+        Adds with offsets= (the noise enters at that window sample) or tile= (the noise is looped from its live end over the rest
+        of the window).  All of them go through ONE clx_addn_windows call (claxon_hip.h), which passes over the batch once: every
+        gain is taken against the signal as it arrives, not against what an earlier Add left, and a cell receives its terms in
+        list order.  One noise read() per distinct source that some window names (None counts as this set), the windows of the
+        Adds that share a source stacked in one read, with this call's length, layout, sample_rate and channels: a looped
+        noise's period is its noise window's valid length, min(what the stream has from starts[k] on, length).  An Add whose
+        stream id is -1 for a window adds
+        nothing there.  With a list return_gains=True appends float32 [B, S], 0 where nothing was added; with a single Add it stays
+        [B].  A single Add with every offset 0 and no tile, not in a list, goes to clx_add_windows exactly as before.  The refusals
+        above apply to each Add; ValueError also for a list that is empty, longer than 16 or holds something else, and for more
+        than 8 distinct sources.
 
         With reverb=Reverb(...) every window is convolved with a room impulse response between the crop (resampling and channels=
         included) and add=, so that noise is added to the reverberant signal and normalize= sees both: one
@@ -3171,8 +3288,7 @@ class StreamSet:
         closed or of another context.  reverb=None is the call without the argument."""
         if normalize is not None and not isinstance(normalize, Norm):
             raise ValueError("read: normalize must be a Norm or None, not %r" % (normalize,))
-        if add is not None and not isinstance(add, Add):
-            raise ValueError("read: add must be an Add or None, not %r" % (add,))
+        adds = _adds_of(add, "read")
         if reverb is not None and not isinstance(reverb, Reverb):
             raise ValueError("read: reverb must be a Reverb or None, not %r" % (reverb,))
         import torch
@@ -3210,8 +3326,9 @@ class StreamSet:
                 k = int(odd[0])
                 raise ValueError("read: no rule brings the %d channels of stream %d to %d (window %d)" % (int(cw[k]), int(sid[k]), ch, k))
         mixed = bool(np.any(cw != ch))                       # (only with channels=K: some window is reduced or replicated)
-        if add is not None:
-            add_src, add_sel = add._plan(self, sid.size, ch, channels, "read")
+        add_plans = [a._plan(self, sid.size, ch, channels, "read") for a in adds]
+        if len({id(src) for src, sel in add_plans if sel.size}) > ADDN_MAX_BATCHES:
+            raise ValueError("read: add names more than %d distinct sources" % ADDN_MAX_BATCHES)
         if reverb is not None:
             rv_sel, rv_taps = reverb._plan(self, sid.size, sample_rate, "read")
         B, dev = sid.size, "cuda:%d" % self.ctx.device
@@ -3225,7 +3342,8 @@ class StreamSet:
         shape = (B, length, ch) if layout == "tc" else (B, ch, length)
         out = torch.empty(shape, dtype=torch.float32, device=dev)
         if B == 0 or length == 0:
-            return (out, torch.from_numpy(valid)) + ((torch.zeros(B, dtype=torch.float32, device=dev),) if return_gains else ())
+            return (out, torch.from_numpy(valid)) + ((torch.zeros(B if isinstance(add, Add) or not adds else (B, len(adds)), dtype=torch.float32, device=dev),)
+                                                     if return_gains else ())
         live = np.nonzero(valid > 0)[0]
         # a live window's source span [lo, hi) in its stream's samples: the window itself, or what the filter reaches from it
         lo, hi = st[live], st[live] + valid[live]
@@ -3277,15 +3395,44 @@ class StreamSet:
             # (out of place; the dry batch stays alive beside `ir` until the call returns, as the noise of add= does)
             dry, out = out, self.ctx.reverb_windows(out, valid, ir.view(rv_sel.size, rv_taps), ir_len.numpy(), index, _LAYOUTS[layout],
                                                     keep_power=reverb.keep_power, method=reverb.method)
-        mixing = add is not None and ch > 0 and add_sel.size > 0
-        # the gains: clx_add_windows writes every one of them when it runs, so they need no fill then -- a fill would run on torch's
-        # stream, unordered against the context's own stream that the launches go to when torch's current stream is the default one
-        gains = None if not return_gains else (torch.empty if mixing else torch.zeros)(B, dtype=torch.float32, device=dev)
-        if mixing:
+        mixing = ch > 0 and any(sel.size > 0 for _, sel in add_plans)
+        listed, S = not isinstance(add, Add), len(adds)
+        # the gains: clx_add_windows and clx_addn_windows write every one of them when they run, so they need no fill then -- a fill
+        # would run on torch's stream, unordered against the context's own stream that the launches go to when torch's current
+        # stream is the default one
+        gains = None if not return_gains else (torch.empty if mixing else torch.zeros)((B, S) if listed and S else B, dtype=torch.float32, device=dev)
+        if mixing and not listed and add.plain:
+            add_src, add_sel = add_plans[0]
             noise, noise_valid = add_src.read(add.stream_ids[add_sel], add.starts[add_sel], length, layout, sample_rate=sample_rate, channels=channels)
             index = np.full(B, -1, dtype=np.int32)
             index[add_sel] = np.arange(add_sel.size, dtype=np.int32)
             self.ctx.add_windows(out, valid, noise, noise_valid.numpy(), index, add.snr_db, _LAYOUTS[layout], gains=gains)
+        elif mixing:
+            # one noise read per distinct source, the windows of the Adds that share it stacked in list order; then S terms a window
+            # in list order (an Add whose stream id is -1 there gives a term that adds nothing), all in one clx_addn_windows call
+            sources, noises, noise_valids = [], [], []
+            batch, index = np.zeros((B, S), dtype=np.int32), np.full((B, S), -1, dtype=np.int32)
+            for s_, (src, sel) in enumerate(add_plans):
+                if sel.size and not any(src is o for o in sources):      # (a source none of whose Adds names a stream is not read)
+                    sources.append(src)
+            for b, src in enumerate(sources):
+                mine = [s_ for s_, (o, _) in enumerate(add_plans) if o is src]
+                ids = np.concatenate([adds[s_].stream_ids[add_plans[s_][1]] for s_ in mine])
+                sts = np.concatenate([adds[s_].starts[add_plans[s_][1]] for s_ in mine])
+                at = 0
+                for s_ in mine:
+                    sel = add_plans[s_][1]
+                    batch[:, s_] = b
+                    index[sel, s_] = at + np.arange(sel.size, dtype=np.int32)
+                    at += sel.size
+                noise, noise_valid = src.read(ids, sts, length, layout, sample_rate=sample_rate, channels=channels)
+                noises.append(noise)
+                noise_valids.append(noise_valid.numpy())
+            offset = np.stack([np.minimum(a.offsets, length) for a in adds], axis=1)     # (at or behind the window's end: an empty cover)
+            loop = np.stack([a.tile for a in adds], axis=1)
+            snr = np.stack([a.snr_db for a in adds], axis=1)
+            self.ctx.addn_windows(out, valid, noises, np.concatenate(noise_valids), np.arange(B + 1, dtype=np.int64) * S, batch.reshape(-1),
+                                  index.reshape(-1), offset.reshape(-1), loop.reshape(-1), snr.reshape(-1), _LAYOUTS[layout], gains=gains)
         if normalize is not None and ch > 0:
             self.ctx.norm_windows(out, valid, _LAYOUTS[layout], normalize)
         return (out, torch.from_numpy(valid)) + ((gains,) if return_gains else ())
@@ -3314,7 +3461,8 @@ class StreamSet:
 
         With add=Add(...) the Add goes to that read() (starts counted at spec.sample_rate, every noise stream brought to one
         channel): the features are those of the noisy waveform, for every spec -- a centred or reflected spec reflects the noisy
-        crop.  valid and valid_frames are the signal's.
+        crop.  valid and valid_frames are the signal's.  add= takes what read()'s takes: one Add, also with offsets= or tile=, or a
+        list of 1..16 of them (one clx_addn_windows call; offsets counted at spec.sample_rate).
 
         With reverb=Reverb(...) the Reverb goes to that read() too (starts and taps counted at spec.sample_rate), in front of the
         Add: the features are those of the reverberant, then noisy, waveform.
@@ -3387,8 +3535,7 @@ class StreamSet:
             raise ValueError("read_mel: vad must be a Vad or None, not %r" % (vad,))
         if return_vad and vad is None:
             raise ValueError("read_mel: return_vad=True needs vad=")
-        if add is not None and not isinstance(add, Add):
-            raise ValueError("read_mel: add must be an Add or None, not %r" % (add,))
+        _adds_of(add, "read_mel")
         if reverb is not None and not isinstance(reverb, Reverb):
             raise ValueError("read_mel: reverb must be a Reverb or None, not %r" % (reverb,))
         if stats is not None and (not isinstance(stats, CmvnStats) or stats._acc is None or stats.ctx is not self.ctx):

@@ -15,6 +15,7 @@
 #include "clx_mel.hip"
 #include "clx_norm.hip"
 #include "clx_add.hip"
+#include "clx_addn.hip"                 // (behind clx_norm.hip and clx_add.hip: the order of the sums and the gain are theirs)
 #include "clx_reverb.hip"
 #include "clx_reverb_fft.hip"
 #include "clx_specaug.hip"
@@ -329,6 +330,9 @@ struct clx_ctx {
     clx_call_scratch norm { "norm", 64, sizeof(uint32_t), sizeof(uint32_t) };
     // clx_add_windows: q, Vs, Vn, j per window; behind them on the device the gains
     clx_call_scratch add { "add", 64, clx_add::kTableBytesDevice, clx_add::kTableBytes };
+    // clx_addn_windows (in bytes): the terms' records, then Vs, the CSR and the covers' hull per window; behind them on the device
+    // the gains
+    clx_call_scratch addn { "addn", 4096, 1, 1 };
     // clx_reverb_windows: clx_add's four arrays, then len and idx per window; behind them on the device the gains
     clx_call_scratch rv { "reverb", 64, clx_reverb::kTableBytesDevice, clx_reverb::kTableBytes };
     // clx_reverb_windows_fft (in bytes): clx_reverb_windows' table, the gains behind it, then the call's partition jobs.  Beside it
@@ -563,6 +567,7 @@ extern "C" void clx_destroy(clx_ctx* ctx) {
     for (clx_mel_spec* sp : ctx->mel_specs) { if (sp->d_tables) (void)hipFree(sp->d_tables); delete sp; }
     ctx->norm.release();
     ctx->add.release();
+    ctx->addn.release();
     ctx->rv.release();
     ctx->rvf.old_dev.push_back(ctx->d_rvf_tw);                 // (the same)
     ctx->rvf.release();
@@ -1858,6 +1863,42 @@ extern "C" int clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uin
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(clx_k_add_apply, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_add::kThreads), 0, stream, (float*)d_data,
                        (const float*)d_noise, (const void*)d_add, (const float*)gain, (uint32_t)n_windows, rows, T, pl.tc, pl.n_tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, s.done(stream));
+    return CLX_OK;
+}
+
+extern "C" int clx_addn_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                                const void* const* d_noise, const size_t* n_noise, uint32_t n_batches, const uint32_t* noise_valid,
+                                const uint32_t* term_first, const clx_addn_term* terms, uint32_t layout, const clx_addn_opts* opts,
+                                void* d_gains, void* stream_) {
+    if (!ctx) return CLX_API_ERROR;
+    clx_addn_plan pl;
+    const char* why = clx_addn_check(d_data, n_windows, rows, T, valid, d_noise, n_noise, n_batches, noise_valid, term_first, terms, layout, opts, &pl);
+    if (why) { ctx->last_error = why; return CLX_API_ERROR; }
+    if (pl.n_chunks == 0) return CLX_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    clx_call_scratch& s = ctx->addn;
+    if (s.begin(ctx, stream, (size_t)pl.table_bytes + pl.n_terms * sizeof(float), (size_t)pl.partials) != CLX_OK) return CLX_API_ERROR;
+    void* const d_tab = s.d; double* const d_part = (double*)s.part.p;
+    clx_addn_fill(s.h, n_windows, rows, T, valid, d_noise, n_noise, n_batches, noise_valid, term_first, terms);
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab, s.h, (size_t)pl.table_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, s.uploaded(stream));
+    float* const gain = (float*)((char*)d_tab + pl.table_bytes);                            // (behind this call's table)
+    const float* x = (const float*)d_data;
+    if (pl.tc)
+        hipLaunchKernelGGL(clx_k_addn_sum_tc, dim3(pl.sum_blocks), dim3(clx_addn::kThreads), 0, stream, x, (const void*)d_tab, d_part,
+                           (uint32_t)n_windows, pl.n_terms, rows, T, pl.n_chunks, pl.units);
+    else
+        hipLaunchKernelGGL(clx_k_addn_sum, dim3(pl.sum_blocks), dim3(clx_addn::kThreads), 0, stream, x, (const void*)d_tab, d_part,
+                           (uint32_t)n_windows, pl.n_terms, rows, T, pl.n_chunks, pl.units);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_addn_gain, dim3(pl.gain_blocks), dim3(clx_addn::kThreads), 0, stream, (const void*)d_tab, (const double*)d_part,
+                       gain, (float*)d_gains, (uint32_t)n_windows, pl.n_terms, rows, pl.n_chunks);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(clx_k_addn_apply, dim3((unsigned)(n_windows * pl.n_tiles)), dim3(clx_addn::kThreads), 0, stream, (float*)d_data,
+                       (const void*)d_tab, (const float*)gain, (uint32_t)n_windows, pl.n_terms, rows, T, pl.tc, pl.n_tiles);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, s.done(stream));
     return CLX_OK;

@@ -707,12 +707,64 @@ int  clx_norm_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t row
  * unknown layout, rows outside 1..8, a null valid, noise_index or snr_db, a valid[k] > T, a noise_index[k] outside -1 ..
  * n_noise - 1, a snr_db[k] that is NaN, one that is -inf or beyond 200 in magnitude, and -- where some noise_index[k] >= 0 -- a
  * null d_data, d_noise or noise_valid and a noise_valid[j] > T.  n_windows == 0, T == 0 or every noise_index[k] == -1 succeeds,
- * launches nothing and leaves d_gains alone.  Not here: tiling a short noise over a long window, several noises in one call,
- * other gain rules (peak, loudness). */
+ * launches nothing and leaves d_gains alone.  Not here: tiling a short noise over a long window and several noises in one call
+ * (both are clx_addn_windows below), other gain rules (peak, loudness). */
 typedef struct { uint32_t reserved; } clx_add_opts;
 int  clx_add_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
                      const void* d_noise, size_t n_noise, const uint32_t* noise_valid, const int32_t* noise_index,
                      const float* snr_db, uint32_t layout, const clx_add_opts* opts, void* d_gains, void* stream);
+/* Several noises added to a dense float32 batch in one pass, each placed at an offset or looped over the window, each at its own
+ * signal-to-noise ratio against the signal AS IT ARRIVES: the MUSAN half of "MUSAN + RIR" -- music or background noise looped over
+ * the utterance (wav-reverberate --duration), babble (several speakers summed), foreground noises dropped in at start times
+ * (--additive-signals --start-times --snrs).  d_data is [n_windows][rows][T] (CLX_WINDOW_CT) or [n_windows][T][rows]
+ * (CLX_WINDOW_TC), rows in 1..8, Vs = valid[k], and is modified in place.
+ *
+ *   noise      n_batches <= 8 noise batches: d_noise[b] (a HOST array of device pointers) is [n_noise[b]][rows][T] or
+ *              [n_noise[b]][T][rows], with the data's layout, rows and T.  noise_valid is one host array, concatenated over the
+ *              batches in order (n_noise[0] + .. + n_noise[n_batches - 1] entries).  No noise batch is ever written; one that
+ *              overlaps d_data is the caller's error and undefined.
+ *   terms      M = term_first[n_windows] terms in CSR form: window k has terms term_first[k] .. term_first[k + 1] - 1 (term_first
+ *              ascends from 0, at most 16 terms a window).  Term m: `batch` (which noise batch), `index` (the noise window in that
+ *              batch; -1: the term adds nothing, and batch is not looked at), `offset` (the window sample at which the noise
+ *              enters), `loop` (0 or 1), `snr_db` (finite within -200 .. 200, or +inf: nothing added).
+ *   cover      P = noise_valid of the term's noise window.  The term covers the window samples off <= t < end, end = Vs with
+ *              loop, else min(Vs, off + P); the cover is empty if off >= Vs or P == 0.  Nc = end - off.  At t the term reads noise
+ *              sample i mod P, i = t - off (without loop i < P anyway): a looped noise starts over at its live end, not at T.
+ *   Es         exactly clx_add_windows' Es over t < Vs of the data as it arrives; every gain of the window is taken from this ONE
+ *              Es -- a later term does not see an earlier one in the signal.
+ *   En_m       the sum over the rows r ascending, from +0.0, of the row sums of (double)n[r][i mod P]^2 for i = 0 .. Nc - 1, each
+ *              row sum in clx_norm_windows' ORDER indexed by i with n = Nc: chunk i / 4096, strand i % 64, the xor fold, the
+ *              chunks' partials ascending from +0.0.  A term with offset 0 and no loop sums what clx_add_windows sums, in its order.
+ *   g_m        q_m = pow(10.0, -(double)snr_db / 10.0) by the host's libm, 0 for +inf (clx_add_windows' q);
+ *              g_m = (float)sqrt((Es * (double)Nc * q_m) / (En_m * (double)Vs)), with clx_add_windows' operations and roundings.
+ *              g_m = +0.0 where index < 0, the cover is empty, Es == 0, En_m == 0 or q_m == 0.  Nothing is clamped (see there).
+ *   cell       a cell with t < Vs becomes the chain x = fmaf(g_m, n_m[r][(t - off_m) mod P_m], x) over the window's terms in
+ *              ascending m, taking those whose cover holds t and whose g_m != 0; one rounding a step.  A cell in no such term's
+ *              cover keeps its word, and so does the padding; a window none of whose terms has g_m != 0 is not rewritten; no data
+ *              cell with t >= Vs is read, no noise cell at or behind its P.  CT and TC of the same data give the same words.
+ *   gains      d_gains (may be NULL) is [M] float32 and receives g_m of every term of a call that launches.
+ *
+ * Not Kaldi's rule: wav-reverberate divides by the power of the whole noise file and of the whole signal.  Here both are means over
+ * the cells that actually meet -- clx_add_windows' rule, kept: 10 log10((Es / Vs) / (g_m^2 En_m / Nc)) = snr_db, and the samples of
+ * a looped noise are counted as often as they sound.  Where a noise covers the whole window once the two rules agree.
+ *
+ * opts is NULL or all zero.  Every array but d_data, the noise batches and d_gains is a host array, staged as clx_add_windows
+ * stages its own (one pinned table a call, a table that has to grow replaced before anything is queued, one event behind the
+ * upload and one behind the last launch), so the call is asynchronous on `stream` (NULL: the context's) and the arrays may be
+ * reused at once.  The partial sums wait in a table of (n_windows + M) * rows * ceil(T / 4096) doubles, the gains in one of M
+ * floats.  No floating-point atomics.  CLX_API_ERROR, each with a clx_last_error text of its own, for opts that are not zero, an
+ * unknown layout, rows outside 1..8, more than 8 batches, a null valid or term_first, a term_first that does not ascend from 0,
+ * more than 16 terms in a window, a valid[k] > T, a null terms with M > 0, a loop other than 0 or 1, a snr_db that is NaN, one that
+ * is -inf or beyond 200 in magnitude, an index below -1 or outside its batch, a batch outside 0 .. n_batches - 1, and -- where some
+ * index >= 0 -- a null d_data, d_noise, noise_valid or named batch and a noise_valid[j] > T.  n_windows == 0, T == 0, M == 0 or
+ * every index == -1 succeeds, launches nothing and leaves d_gains alone.  Not here: Kaldi's whole-file power rule, peak or
+ * loudness rules, fades at the loop points, reverberated noises, noise batches of another T, rows or layout. */
+typedef struct { uint32_t reserved; } clx_addn_opts;
+typedef struct { int32_t batch; int32_t index; uint32_t offset; uint32_t loop; float snr_db; } clx_addn_term;
+int  clx_addn_windows(clx_ctx* ctx, void* d_data, size_t n_windows, uint32_t rows, uint32_t T, const uint32_t* valid,
+                      const void* const* d_noise, const size_t* n_noise, uint32_t n_batches, const uint32_t* noise_valid,
+                      const uint32_t* term_first, const clx_addn_term* terms, uint32_t layout, const clx_addn_opts* opts,
+                      void* d_gains, void* stream);
 /* A dense float32 batch of windows convolved with room impulse responses, out of place on the device: reverberation, the step
  * between the crop and clx_add_windows (noise is added to the reverberant speech).  d_data is [n_windows][rows][T] (CLX_WINDOW_CT)
  * or [n_windows][T][rows] (CLX_WINDOW_TC), rows in 1..8, and is never written; d_out has the same shape and layout, must not
